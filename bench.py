@@ -25,6 +25,11 @@ The 100 clients are dealt round-robin over the N ranks, so total work is fixed: 
 
   python bench.py --gpus N --steps K --warmup W
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K rounds and prints one JSON line; `--dump-outputs DIR`
+also writes the last timed round's results as DIR/*.npy. `--full` is where any measurement
+beyond the headline figure belongs (none today: baselines are recorded constants, the other
+workloads are separate `--workload` runs, microbenchmarks live under bench/).
 """
 
 from __future__ import annotations
@@ -94,6 +99,15 @@ def main() -> None:
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="diagnostic: time rank 0's share of an N-rank round alone on one GPU "
                          "(collectives are no-ops; not the benchmark contract)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed round returned to its caller as "
+                         "DIR/<name>.npy (global_parameters: the broadcast model, float32; round_metrics: "
+                         "test loss / accuracy, float64). Same arguments => same inputs (seeded), so two builds "
+                         "compare output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond the headline figure. A plain run "
+                         "already does nothing but set up, warm up and time the rounds (the baseline it "
+                         "compares with is a recorded constant), so today this adds nothing")
     args = ap.parse_args()
     if args.emulate_world and args.workload != "fedavg_resnet18":
         ap.error("--emulate-world supports the fedavg_resnet18 workload only")
@@ -183,6 +197,8 @@ def main() -> None:
     # the timed rounds' metrics rows, taken before any stage-2 round appends its own (FedOBD:
     # per-round comm bytes / phases / accuracy describe stage 1 only; stage 2 is reported apart)
     rows = sess.metrics[m0:]
+    if args.dump_outputs and comm.rank == 0:
+        dump_outputs(args.dump_outputs, theta, rows[-1] if rows else {})
     stage2 = None
     if wl.get("stage2") and not args.no_stage2:
         # FedOBD: the timed rounds above are stage 1; the whole second phase (all clients,
@@ -259,6 +275,27 @@ def main() -> None:
     # tear the process group down on every rank (an exiting rank with a live gloo/RCCL group
     # aborts in the communicator's destructor)
     shutdown()
+
+
+# --dump-outputs: at most this many elements of the global model are written (float32: 48 MB);
+# a larger model (ResNet-50) is sampled at fixed, seeded positions
+DUMP_MAX_ELEMENTS = 12_000_000
+
+
+def dump_outputs(out_dir: str, theta, row: dict) -> None:
+    """What the last timed round handed back to its caller: the global parameters as the clients
+    receive them (`Session.run_one_round`'s return value) and the round's test metrics row."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = theta.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMENTS:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_ELEMENTS, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "global_parameters.npy"), flat.to(torch.float32).cpu().numpy())
+    metrics = [float(row[k]) if row.get(k) is not None else float("nan") for k in ("test_loss", "test_accuracy")]
+    np.save(os.path.join(out_dir, "round_metrics.npy"), np.asarray(metrics, dtype=np.float64))
 
 
 def workload_config(args, rounds: int) -> dict:
