@@ -498,6 +498,22 @@ void quant_unpack_acc(const uint8_t* codes, const int* seg, const int64_t* seg_o
                       const uint8_t* bits, const float* lo, const float* scale, const int64_t* seg_byte_off,
                       const int64_t* row_off, int K, int nseg, long P, const double* w, double* acc, hipStream_t s);
 
+// ---- top-k sparse payloads (csrc/topk.hip, ops/compress.py SparsePayload)
+// Exact top-k by |u| of every row (ties to the lower index; vbits: one eligibility bit per element,
+// uint32 words LSB-first): idx [K][k] int32 ascending, val [K][k]. ef: u ← delta + u first and the
+// selected positions of u end up zero (error feedback); else u is only read and delta unused.
+// Workspaces: hist [K][2048] uint32 ZEROED (left zeroed), state [K][2], cnt and excl
+// [K][ceil(P / TOPK_CHUNK)][2] uint32. Rows 16-B aligned, P % 4 == 0.
+#define TOPK_CHUNK 4096
+void topk_pack(const float* delta, long ld_d, float* u, long ld_u, int ef, const uint32_t* vbits, uint32_t* hist,
+               uint32_t* state, uint32_t* cnt, uint32_t* excl, int* idx, float* val, int K, long P, int k,
+               hipStream_t s);
+// out [K][P] (row stride ld) = 0, then out[row][idx] = val
+void topk_decode(const int* idx, const float* val, float* out, long ld, int K, long P, int k, hipStream_t s);
+// acc [P] fp64 += Σ_row w[row]·val scattered at idx, rows added in order (bitwise reproducible)
+void topk_accumulate(const int* idx, const float* val, const double* w, double* acc, int K, long P, int k,
+                     hipStream_t s);
+
 // out[k][r][c] = keep(k, r, c) ? x·scale : 0 over [K][rows][N] (row stride ld), the dropout rule of
 // the GEMM epilogue; seeds [K]. f32: fp32 (else bf16) tensors.
 void dropout_apply(const void* x, void* out, int K, long rows, int N, long ld, const uint32_t* seeds, float p,

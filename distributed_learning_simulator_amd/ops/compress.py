@@ -14,6 +14,10 @@ Wire bytes per client are the sizes of those buffers (`QuantPayload.row_bytes`),
 The server either decodes to dense rows or, for FedAvg-style weighted sums, dequantises inside
 the fp64 accumulation kernel (`accumulate`: no dense [K, P] materialisation).
 
+`SparsePayload` (fed_topk, csrc/topk.hip) is the sparse member of the family: per client the k
+largest-|u| elements as int32 indices + fp32 values, 8k bytes, with the same decode / accumulate
+interface; `pack_topk_ef` also keeps the error-feedback residual.
+
 Codes:
 - stochastic (FedPAQ / fed_obd_sq, QSGD with 255 signed levels = 8 bits, ops.quant): lo = −‖x‖,
   scale = ‖x‖/127, q = clamp(floor((x − lo)/scale + u), 0, 254), with u the shared per-element
@@ -40,13 +44,32 @@ class LayoutMeta:
     seg_numel: torch.Tensor  # int64 [nseg]
     nseg: int
     P: int
+    _vbits: torch.Tensor | None = None
+    _num_params: int = -1
+
+    @property
+    def num_params(self) -> int:
+        if self._num_params < 0:
+            self._num_params = int(self.seg_numel.sum())
+        return self._num_params
+
+    def valid_bits(self) -> torch.Tensor:
+        """int32 [ceil(P / 32)]: bit i & 31 of word i >> 5 is set iff element i belongs to a tensor
+        (the eligibility mask of the top-k kernels; built once per layout)."""
+        if self._vbits is None:
+            v = self.seg_ids < self.nseg
+            v = torch.cat([v, v.new_zeros((-self.P) % 32)]).view(-1, 32).long()
+            w = (v << torch.arange(32, device=v.device)).sum(1)
+            self._vbits = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
+        return self._vbits
 
     @classmethod
     def of(cls, layout, device) -> "LayoutMeta":
         off = torch.tensor([e.offset for e in layout.entries], dtype=torch.int64, device=device)
         numel = torch.tensor([e.numel for e in layout.entries], dtype=torch.int64, device=device)
         assert layout.padded_size % 8 == 0 and all(e.offset % 8 == 0 for e in layout.entries)
-        return cls(layout.segment_ids(device), off, numel, len(layout.entries), layout.padded_size)
+        return cls(layout.segment_ids(device), off, numel, len(layout.entries), layout.padded_size,
+                   _num_params=layout.num_params)
 
 
 @dataclass
@@ -237,3 +260,97 @@ def _unpack_torch(p: QuantPayload) -> torch.Tensor:
         v = torch.where(lane[None, :] < nn[:, None], v, torch.zeros_like(v))
         out[k].view(-1, 8)[tt] = v
     return out
+
+
+# ------------------------------------------------------------------ top-k sparse payloads
+@dataclass
+class SparsePayload:
+    """Top-k upload of K clients: per row the k selected flat (padded-layout) indices, ascending,
+    and the values at them, verbatim. Selection rule (CPU oracle below ≡ csrc/topk.hip): the key of
+    element i is bits(u[i]) & 0x7fffffff; inter-tensor padding is never eligible; the k eligible
+    elements with the largest keys are selected, ties at the threshold key go to the lower index."""
+
+    idx: torch.Tensor  # int32 [K, k]
+    val: torch.Tensor  # fp32 [K, k]
+    meta: LayoutMeta
+    k: int
+
+    @property
+    def K(self) -> int:
+        return self.idx.shape[0]
+
+    def row_bytes(self) -> list[int]:
+        """Per client: its int32 indices + its fp32 values."""
+        per = self.idx[0].numel() * self.idx.element_size() + self.val[0].numel() * self.val.element_size()
+        return [per] * self.K
+
+    def decode(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        K, P = self.K, self.meta.P
+        if out is None:
+            out = torch.empty((K, P), dtype=torch.float32, device=self.val.device)
+        assert out.shape == (K, P) and out.dtype == torch.float32 and out.stride(1) == 1
+        if backend.get(out) is ref:
+            out.zero_()
+            out.scatter_(1, self.idx.long(), self.val)
+            return out
+        from . import hip
+
+        hip.topk_decode(self, out)
+        return out
+
+    def accumulate(self, acc: torch.Tensor, w: torch.Tensor) -> None:
+        """acc [P] fp64 += Σ_k w[k]·S(u_k), clients added in row order (work ∝ K·k, not K·P)."""
+        assert acc.dtype == torch.float64 and acc.shape == (self.meta.P,)
+        w = w.to(acc.device, torch.float64).contiguous()
+        if backend.get(acc) is ref:
+            acc += (w[:, None] * self.decode().double()).sum(0)
+            return
+        from . import hip
+
+        hip.topk_accumulate(self, w, acc)
+
+
+def _check_topk(u: torch.Tensor, meta: LayoutMeta, k: int) -> None:
+    assert u.dim() == 2 and u.shape[1] == meta.P and u.dtype == torch.float32 and u.stride(1) == 1
+    assert meta.P < 2 ** 31, "top-k indices are int32"
+    assert 1 <= k <= meta.num_params, f"k = {k} outside [1, num_params]"
+
+
+def _select_torch(u: torch.Tensor, meta: LayoutMeta, k: int) -> SparsePayload:
+    """The oracle: torch.topk over the int64 composite (key << 32) | (0xffffffff − i), whose values
+    are unique (no dependence on torch's tie order); ineligible elements get −1."""
+    P = meta.P
+    key = u.contiguous().view(torch.int32).long() & 0x7FFFFFFF
+    i = torch.arange(P, device=u.device)
+    comp = (key << 32) | (0xFFFFFFFF - i)[None, :]
+    comp = torch.where((meta.seg_ids < meta.nseg)[None, :], comp, torch.full_like(comp, -1))
+    idx = comp.topk(k, dim=1).indices.sort(dim=1).values
+    return SparsePayload(idx.to(torch.int32), u.gather(1, idx), meta, k)
+
+
+def pack_topk(u: torch.Tensor, meta: LayoutMeta, k: int) -> SparsePayload:
+    """Top-k selection of rows u [K, P] (u is not modified)."""
+    _check_topk(u, meta, k)
+    if backend.get(u) is ref:
+        return _select_torch(u, meta, k)
+    from . import hip
+
+    idx, val = hip.topk_pack(None, u, meta, k)
+    return SparsePayload(idx, val, meta, k)
+
+
+def pack_topk_ef(delta: torch.Tensor, err: torch.Tensor, meta: LayoutMeta, k: int) -> SparsePayload:
+    """Error-feedback top-k: selects from u = delta + err and leaves err ← u − S(u) in place (u with
+    the selected entries zeroed). delta [K, P] is only read; err [K, P] are the residual rows."""
+    _check_topk(delta, meta, k)
+    _check_topk(err, meta, k)
+    assert err.shape == delta.shape and err.data_ptr() != delta.data_ptr()
+    if backend.get(delta) is ref:
+        err += delta
+        p = _select_torch(err, meta, k)
+        err.scatter_(1, p.idx.long(), 0.0)
+        return p
+    from . import hip
+
+    idx, val = hip.topk_pack(delta, err, meta, k)
+    return SparsePayload(idx, val, meta, k)

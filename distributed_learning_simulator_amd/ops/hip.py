@@ -1412,6 +1412,47 @@ def quant_unpack_acc(p, w, acc):
     _C.quant_unpack_acc(_p(p.codes), *_payload_args(p), p.K, p.meta.nseg, p.meta.P, _p(w), _p(acc), _s())
 
 
+def _rows16(t, name):
+    _check(t, F32, contiguous=False, name=name)
+    assert t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0, f"{name}: rows must be 16-B aligned"
+
+
+def topk_pack(delta, u, meta, k: int):
+    """csrc/topk.hip: (idx int32 [K, k] ascending, val fp32 [K, k]) of the k largest-|u| eligible
+    elements per row. delta None: u is only read. Else u ← delta + u first and the selected
+    positions of u end up zero (error feedback)."""
+    K, P = u.shape
+    assert P == meta.P and P % 4 == 0 and 1 <= k <= P
+    _rows16(u, "u")
+    if delta is not None:
+        _rows16(delta, "delta")
+        assert delta.shape == u.shape
+    dev = u.device
+    nchunks = -(-P // _C.topk_chunk())
+    hist = torch.zeros((K, 2048), dtype=torch.int32, device=dev)
+    ws = torch.empty((2 * K * nchunks * 2 + 2 * K,), dtype=torch.int32, device=dev)
+    cnt, excl, state = ws[: 2 * K * nchunks], ws[2 * K * nchunks : 4 * K * nchunks], ws[4 * K * nchunks :]
+    idx = torch.empty((K, k), dtype=torch.int32, device=dev)
+    val = torch.empty((K, k), dtype=torch.float32, device=dev)
+    _C.topk_pack(_p(delta), delta.stride(0) if delta is not None else 0, _p(u), u.stride(0), int(delta is not None),
+                 _p(meta.valid_bits()), _p(hist), _p(state), _p(cnt), _p(excl), _p(idx), _p(val), K, P, k, _s())
+    return idx, val
+
+
+def topk_decode(p, out):
+    _rows16(out, "out")
+    _check(p.idx, torch.int32, name="idx")
+    _check(p.val, F32, name="val")
+    _C.topk_decode(_p(p.idx), _p(p.val), _p(out), out.stride(0), p.K, p.meta.P, p.k, _s())
+
+
+def topk_accumulate(p, w, acc):
+    assert w.dtype == torch.float64 and w.numel() == p.K and w.is_cuda and acc.is_contiguous() and acc.is_cuda
+    _check(p.idx, torch.int32, name="idx")
+    _check(p.val, F32, name="val")
+    _C.topk_accumulate(_p(p.idx), _p(p.val), _p(w), _p(acc), p.K, p.meta.P, p.k, _s())
+
+
 # ---------------------------------------------------------------------- GNN sampling
 def _hmix_int(h: int) -> int:
     h &= 0x7FFFFFFF

@@ -8,7 +8,10 @@ Here the residual is a per-client row of a device buffer: each round a client up
 S(Δ + e) and keeps e ← (Δ + e) − S(Δ + e). The residual lives on the rank that trains the
 client, so the client→rank assignment must be stable across rounds (full participation, or
 one rank). `TopKErrorFeedbackWorker` is a concrete sparsifier (largest-|x| fraction per
-client row; wire bytes = k values + k int32 indices).
+client row; wire bytes = k values + k int32 indices). `PackedTopKWorker` (method `fed_topk`) is
+the full form: an exact, tie-ordered selection by the hand-written kernels of csrc/topk.hip into
+a packed `ops.compress.SparsePayload` that the server accumulates directly; no dense sparse
+rows exist on the client side.
 """
 
 from __future__ import annotations
@@ -16,6 +19,7 @@ from __future__ import annotations
 import torch
 
 from ..message import CohortMessage
+from ..ops import compress
 from .aggregation_worker import AggregationWorker
 
 
@@ -36,14 +40,17 @@ class ErrorFeedbackWorker(AggregationWorker):
         """rows [K,P] (Δ + e) → (sparse rows [K,P] with zeros where not sent, wire bytes per row)."""
         raise NotImplementedError
 
-    def _error_rows(self, wave: list[int], P: int, device) -> torch.Tensor:
+    def _ensure_error(self, P: int, device) -> torch.Tensor:
         if self._error is None:
             W = self.config.worker_number
             sel = self.config.algorithm_kwargs.get("random_client_number", W) or W
             world = self.session.comm.world if self.session is not None else 1
             assert sel >= W or world == 1, "error feedback residuals need a stable client→rank assignment"
             self._error = torch.zeros((W, P), dtype=torch.float32, device=device)
-        return self._error[torch.tensor(wave, device=device)]
+        return self._error
+
+    def _error_rows(self, wave: list[int], P: int, device) -> torch.Tensor:
+        return self._ensure_error(P, device)[torch.tensor(wave, device=device)]
 
     def _get_sent_data(self, wave, theta_g, stats) -> CohortMessage:
         msg = super()._get_sent_data(wave, theta_g, stats)
@@ -71,3 +78,39 @@ class TopKErrorFeedbackWorker(ErrorFeedbackWorker):
         out = torch.zeros_like(rows)
         out.scatter_(1, top, rows.gather(1, top))
         return out, [k * 8] * rows.shape[0]
+
+
+class PackedTopKWorker(ErrorFeedbackWorker):
+    """Top-k error feedback with a packed upload: `ops.compress.pack_topk_ef` selects from
+    Δ + e, writes the (idx, val) payload and leaves the residual e ← (Δ + e) − S(Δ + e) in
+    `_error`, in place when the wave's clients are consecutive rows of it."""
+
+    def __init__(self, config, endpoint, session=None, **kwargs):
+        super().__init__(config, endpoint, session, **kwargs)
+        self.ratio = float(config.algorithm_kwargs.get("topk_ratio", 0.01))
+        self._meta: compress.LayoutMeta | None = None
+
+    def topk(self) -> int:
+        return max(1, int(self.trainer.layout.num_params * self.ratio))
+
+    def _get_sent_data(self, wave, theta_g, stats) -> CohortMessage:
+        msg = AggregationWorker._get_sent_data(self, wave, theta_g, stats)
+        rows = msg.data
+        K, P = rows.shape
+        if self._meta is None or self._meta.seg_ids.device != rows.device:
+            self._meta = compress.LayoutMeta.of(self.trainer.layout, rows.device)
+        error = self._ensure_error(P, rows.device)
+        if list(wave) == list(range(wave[0], wave[0] + K)):
+            payload = compress.pack_topk_ef(rows, error[wave[0] : wave[0] + K], self._meta, self.topk())
+        else:
+            idx = torch.tensor(wave, device=rows.device)
+            err = error[idx]
+            payload = compress.pack_topk_ef(rows, err, self._meta, self.topk())
+            error[idx] = err
+        # the upload is the packed payload (topology/endpoints._attach); the dense rows stay only
+        # as the receiver's decode target
+        msg.payload = payload
+        msg.extra["decode_into"] = rows
+        msg.data = None
+        msg.extra["wire_bytes"] = payload.row_bytes()
+        return msg

@@ -21,5 +21,7 @@ $S --config-name fed_dropout_avg/cifar100.yaml ++fed_dropout_avg.round=1 ++fed_d
    ++fed_dropout_avg.worker_number=2 ++fed_dropout_avg.algorithm_kwargs.random_client_number=2
 $S --config-name fed_paq/cifar100.yaml ++fed_paq.round=1 ++fed_paq.epoch=1 ++fed_paq.worker_number=2 \
    ++fed_paq.algorithm_kwargs.random_client_number=2
+# top-k sparsified uploads with error feedback (packed payload)
+$S --config-name fed_topk/mnist.yaml ++fed_topk.round=1 ++fed_topk.epoch=1 ++fed_topk.worker_number=2
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
