@@ -514,6 +514,14 @@ void topk_decode(const int* idx, const float* val, float* out, long ld, int K, l
 void topk_accumulate(const int* idx, const float* val, const double* w, double* acc, int K, long P, int k,
                      hipStream_t s);
 
+// ---- robust aggregation (csrc/robust.hip, ops/ref.py trimmed_sum)
+// out[c] (fp64, c < P) = the n values of column c of x [n][P] (row stride ld, rows 16-B aligned,
+// P % 4 == 0) sorted by the signed key bits ^ ((bits >> 31) & 0x7fffffff), the b lowest and b highest
+// dropped, the other n − 2b added as doubles in ascending order from +0.0; a NaN sum is the canonical
+// 0x7ff8000000000000. 1 ≤ n ≤ TRIM_MAX_ROWS, 0 ≤ 2b < n. One launch.
+#define TRIM_MAX_ROWS 512
+void trimmed_sum(const float* x, long ld, int n, int b, long P, double* out, hipStream_t s);
+
 // out[k][r][c] = keep(k, r, c) ? x·scale : 0 over [K][rows][N] (row stride ld), the dropout rule of
 // the GEMM epilogue; seeds [K]. f32: fp32 (else bf16) tensors.
 void dropout_apply(const void* x, void* out, int K, long rows, int N, long ld, const uint32_t* seeds, float p,

@@ -7,6 +7,7 @@
 | broadcast_rows       | load_parameters of θ_g into every client (`util/model.py:6-23`)|
 | delta_rows           | ModelCache.get_parameter_diff (K4, `util/model_cache.py:30-36`)|
 | weighted_sum         | FedAVGAlgorithm accumulate (K6, `fed_avg_algorithm.py:39-52`)  |
+| trimmed_sum          | — (robust aggregation: trimmed mean / median, Yin et al. 2018)  |
 | mix_rows             | Shapley subset models (K8, `aggregation_algorithm.py:30-50`)   |
 | masked_weighted_sum  | FedDropoutAvg aggregation (K10, `fed_dropout_avg/algorithm.py`)|
 | dropout_mask         | FedDropoutAvg Bernoulli mask (K9, `fed_dropout_avg/worker.py`) |
@@ -75,6 +76,15 @@ def delta_rows(theta_rows, base, out=None):
 def weighted_sum(x, w, out=None):
     """out (fp64 [P]; zeros if None) += Σ_k w_k x[k,:], fp64 accumulation. Returns `out`."""
     return backend.get(x).weighted_sum(x, w, out)
+
+
+def trimmed_sum(x, b: int, out=None):
+    """fp64 [P] coordinate-wise trimmed sum of the rows of x [n, P]: per column the n values sorted
+    by the signed key bits ^ ((bits >> 31) & 0x7fffffff), the b lowest and b highest dropped, the
+    other n − 2b added as doubles in ascending order from +0.0 (b = 0: the unweighted sum; b =
+    (n − 1) // 2: the median times 1 or 2). NaN and ±inf uploads are just extreme values. 1 ≤ n ≤
+    512 and 0 ≤ 2b < n, else ValueError. The kernel and the oracle agree bit for bit."""
+    return backend.get(x).trimmed_sum(x, b, out)
 
 
 def mix_rows(x, w, out_dtype):

@@ -1584,6 +1584,22 @@ def weighted_sum(x, w, out=None):
     return out
 
 
+def trimmed_sum(x, b: int, out=None):
+    """csrc/robust.hip: fp64 [P] coordinate-wise trimmed sum of the rows of x [n, P] (sorted by
+    the signed key of `ops.ref.trim_keys`, b lowest and b highest dropped, the rest added in
+    ascending order in fp64). Written into out[:P] if given; out[P:] is not touched."""
+    n, P, ld = _row_args(x)
+    ref.check_trim(n, int(b))
+    _check(x, F32, contiguous=False, name="x")
+    assert ld % 4 == 0 and x.data_ptr() % 16 == 0, "x: rows must be 16-B aligned"
+    if out is None:
+        out = torch.empty(P, dtype=torch.float64, device=x.device)
+    _check(out, torch.float64, name="out")
+    assert out.dim() == 1 and out.numel() >= P
+    _C.trimmed_sum(_p(x), ld, n, int(b), P, _p(out), _s())
+    return out
+
+
 def mix_rows(x, w, out_dtype=BF16):
     """[M, P] = W[M, K] · x[K, P]: subset models for Shapley utilities, emitted in the eval
     compute dtype (bf16 or fp32) by one native pass that reads each x row once per 32 models;

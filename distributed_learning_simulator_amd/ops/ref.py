@@ -427,6 +427,46 @@ def weighted_sum(x, w, out=None):
     return out.add_(acc)
 
 
+TRIM_MAX_ROWS = 512  # csrc/dls.h
+
+
+def trim_keys(x):
+    """Signed int32 sort keys of fp32 values: bits ^ ((bits >> 31) & 0x7fffffff). Monotone over the
+    non-NaN floats, −0 below +0, negative-sign NaNs below −inf, positive-sign NaNs above +inf; equal
+    keys are equal bit patterns."""
+    bits = x.contiguous().view(torch.int32)
+    return bits ^ ((bits >> 31) & 0x7FFFFFFF)
+
+
+def check_trim(n: int, b: int) -> None:
+    if not 1 <= n <= TRIM_MAX_ROWS:
+        raise ValueError(f"trimmed_sum supports 1 to {TRIM_MAX_ROWS} rows, got {n}")
+    if not 0 <= 2 * b < n:
+        raise ValueError(f"trimmed_sum needs 0 <= 2b < n, got b={b}, n={n}")
+
+
+def trimmed_sum(x, b, out=None):
+    """Coordinate-wise trimmed sum (the oracle of csrc/robust.hip): per column of x [n, P] the values
+    are sorted by `trim_keys`, the b lowest and b highest dropped and the other n − 2b added as
+    doubles one at a time in ascending order from +0.0. A NaN sum is the canonical quiet NaN
+    (0x7ff8000000000000). Returns fp64 [P] (written into out[:P] if given)."""
+    n, P = x.shape
+    check_trim(n, b)
+    assert x.dtype == torch.float32
+    order = torch.sort(trim_keys(x), dim=0).indices
+    rows = torch.gather(x, 0, order)
+    acc = torch.zeros(P, dtype=torch.float64, device=x.device)
+    for r in range(b, n - b):
+        acc = acc + rows[r].double()
+    nan = torch.tensor(0x7FF8000000000000, dtype=torch.int64, device=x.device).view(torch.float64)
+    acc = torch.where(acc.isnan(), nan, acc)
+    if out is None:
+        return acc
+    assert out.dtype == torch.float64 and out.dim() == 1 and out.numel() >= P
+    out[:P].copy_(acc)
+    return out
+
+
 def mix_rows(x, w, out_dtype=torch.float32):
     """Subset models W[M, K] · x[K, P] (fp64 accumulation), cast to `out_dtype`."""
     return (w.double().to(x.device) @ x.double()).to(out_dtype)

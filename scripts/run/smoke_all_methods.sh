@@ -23,5 +23,10 @@ $S --config-name fed_paq/cifar100.yaml ++fed_paq.round=1 ++fed_paq.epoch=1 ++fed
    ++fed_paq.algorithm_kwargs.random_client_number=2
 # top-k sparsified uploads with error feedback (packed payload)
 $S --config-name fed_topk/mnist.yaml ++fed_topk.round=1 ++fed_topk.epoch=1 ++fed_topk.worker_number=2
+# robust aggregation (coordinate-wise trimmed mean / median) with Byzantine clients
+$S --config-name fed_trimmed_mean/mnist.yaml ++fed_trimmed_mean.round=1 ++fed_trimmed_mean.epoch=1 ++fed_trimmed_mean.worker_number=5 \
+   ++fed_trimmed_mean.algorithm_kwargs.byzantine_number=1 ++fed_trimmed_mean.debug=True
+$S --config-name fed_median/mnist.yaml ++fed_median.round=1 ++fed_median.epoch=1 ++fed_median.worker_number=5 \
+   ++fed_median.algorithm_kwargs.byzantine_number=1 ++fed_median.algorithm_kwargs.byzantine_attack=nan ++fed_median.debug=True
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
