@@ -522,6 +522,21 @@ void topk_accumulate(const int* idx, const float* val, const double* w, double* 
 #define TRIM_MAX_ROWS 512
 void trimmed_sum(const float* x, long ld, int n, int b, long P, double* out, hipStream_t s);
 
+// ---- Krum pairwise distances (csrc/krum.hip, ops/ref.py pairwise_sq_dists)
+// out[i][j] (fp64 [n][n]) = Σ_p fl64(d·d), d = fl64(double(x[i][p]) − double(x[j][p])), multiply and add
+// rounded separately (no FMA), in this order: the columns are cut into spans of PAIR_SPAN columns
+// and the spans into groups of PAIR_GROUP consecutive spans; a span's terms are added one at a time
+// in ascending column order from +0.0, a group's span sums in ascending span order from +0.0, and
+// the group sums in ascending group order from +0.0. x [n][P]: row stride ld, rows 16-B aligned,
+// P % 4 == 0, 1 ≤ n ≤ TRIM_MAX_ROWS. `spw` (1 or PAIR_GROUP, pairwise_spans_per_wg: the default) is
+// the number of spans one workgroup adds up itself; it changes the scratch size (pairwise_ws_doubles
+// doubles at `ws`), never a bit of the result. Two launches, no atomics.
+#define PAIR_SPAN 4096
+#define PAIR_GROUP 8
+int pairwise_spans_per_wg(int n, long P);
+long pairwise_ws_doubles(int n, long P, int spw);
+void pairwise_sq_dists(const float* x, long ld, int n, long P, double* ws, int spw, double* out, hipStream_t s);
+
 // out[k][r][c] = keep(k, r, c) ? x·scale : 0 over [K][rows][N] (row stride ld), the dropout rule of
 // the GEMM epilogue; seeds [K]. f32: fp32 (else bf16) tensors.
 void dropout_apply(const void* x, void* out, int K, long rows, int N, long ld, const uint32_t* seeds, float p,

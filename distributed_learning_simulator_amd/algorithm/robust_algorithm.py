@@ -31,12 +31,15 @@ from .aggregation_algorithm import AggregationAlgorithm
 
 class TrimmedMeanAlgorithm(AggregationAlgorithm):
     median: bool = False
+    track_ids: bool = False  # Krum: the client ids travel with the rows (`_round_ids`)
     expected_kind: str = "delta"  # set by the session: a rank without clients still knows the kind
 
     def __init__(self) -> None:
         super().__init__()
         self._store: torch.Tensor | None = None  # [capacity, P] fp32, kept across rounds
         self._n = 0  # rows of this round held by this rank
+        self._ids: list[int] = []  # their client ids, in row order
+        self._round_ids: list[int] = []  # ids of the rows `_gather_rows` returned (track_ids)
         self._kind: str | None = None
         self.last_fp64: torch.Tensor | None = None
         self.last_trim: tuple[int, int] = (0, 0)  # (n, b) of the last aggregation
@@ -64,13 +67,16 @@ class TrimmedMeanAlgorithm(AggregationAlgorithm):
         store = self._reserve(self._n + K)
         store[self._n : self._n + K].copy_(rows)
         self._n += K
+        self._ids.extend(int(c) for c in msg.client_ids)
 
     # ------------------------------------------------------------------ ranks
     def _gather_rows(self) -> torch.Tensor:
         """All ranks' rows of the round as one [n, P]. The per-rank row counts and the host-side
-        round flags (end_training, whether a rank carries other_data) ride in one small all-gather."""
+        round flags (end_training, whether a rank carries other_data) ride in one small all-gather;
+        with `track_ids` the client ids follow in a second one, padded like the rows."""
         comm, P = self.comm, self.layout.padded_size
         local = self._store[: self._n] if self._n else torch.empty((0, P), dtype=torch.float32, device=self.device)
+        self._round_ids = list(self._ids)
         if not comm.is_distributed:
             return local
         head = torch.tensor([self._n, 1 if self._end_training else 0, 1 if self._other_data else 0],
@@ -86,6 +92,10 @@ class TrimmedMeanAlgorithm(AggregationAlgorithm):
         m = max(counts)
         if m == 0:
             return local
+        if self.track_ids:
+            ids = torch.full((m,), -1, dtype=torch.int64, device=self.device)
+            ids[: self._n] = torch.tensor(self._ids, dtype=torch.int64, device=self.device)
+            self._round_ids = [int(c) for p, k in zip(comm.all_gather(ids), counts) for c in p[:k].tolist()]
         padded = torch.zeros((m, P), dtype=torch.float32, device=self.device)
         padded[: self._n].copy_(local)
         parts = comm.all_gather(padded)
@@ -131,6 +141,7 @@ class TrimmedMeanAlgorithm(AggregationAlgorithm):
 
     def _reset_round(self) -> None:
         self._n = 0
+        self._ids = []
         self._kind = None
 
     def clear_worker_data(self) -> None:

@@ -8,6 +8,7 @@
 | delta_rows           | ModelCache.get_parameter_diff (K4, `util/model_cache.py:30-36`)|
 | weighted_sum         | FedAVGAlgorithm accumulate (K6, `fed_avg_algorithm.py:39-52`)  |
 | trimmed_sum          | — (robust aggregation: trimmed mean / median, Yin et al. 2018)  |
+| pairwise_sq_dists    | — (Krum / Multi-Krum distances, Blanchard et al. 2017)           |
 | mix_rows             | Shapley subset models (K8, `aggregation_algorithm.py:30-50`)   |
 | masked_weighted_sum  | FedDropoutAvg aggregation (K10, `fed_dropout_avg/algorithm.py`)|
 | dropout_mask         | FedDropoutAvg Bernoulli mask (K9, `fed_dropout_avg/worker.py`) |
@@ -85,6 +86,40 @@ def trimmed_sum(x, b: int, out=None):
     (n − 1) // 2: the median times 1 or 2). NaN and ±inf uploads are just extreme values. 1 ≤ n ≤
     512 and 0 ≤ 2b < n, else ValueError. The kernel and the oracle agree bit for bit."""
     return backend.get(x).trimmed_sum(x, b, out)
+
+
+def pairwise_sq_dists(x, out=None):
+    """fp64 [n, n] squared L2 distances between the rows of x [n, P] fp32 (row stride ≥ P), the hot
+    path of Krum / Multi-Krum (csrc/krum.hip; oracle and CPU path ops/ref.py).
+
+    term(i, j, p) = fl64(d · d) with d = fl64(double(x[i, p]) − double(x[j, p])); the multiply and the
+    add that follows are rounded separately (no FMA); denormal inputs are not flushed. D[i, j] adds
+    the terms in an order fixed by the column index alone: the columns are cut into spans of W =
+    ref.PAIR_SPAN = 4096 columns (the last may be shorter) and the spans into groups of G =
+    ref.PAIR_GROUP = 8 consecutive spans;
+      span sum  = the span's terms added one at a time in ascending column order from +0.0,
+      group sum = the group's span sums added in ascending span order from +0.0,
+      D[i, j]   = the group sums added in ascending group order from +0.0.
+    Nothing depends on n, the row order, the launch geometry, the device or the rank count: D[i, i]
+    is +0.0 for a finite row, D[i, j] and D[j, i] have the same bits, a row permutation permutes D,
+    zero columns change nothing, D is finite where both rows are, NaN / ±inf follow IEEE (NaN payload
+    bits are not part of the contract). No float atomics: bitwise reproducible, and the kernel and
+    the oracle agree bit for bit. 1 ≤ n ≤ 512, else ValueError."""
+    return backend.get(x).pairwise_sq_dists(x, out)
+
+
+def krum_select(D, f: int, m: int, ids) -> list:
+    """Row indices (sorted by client id) of the m uploads with the smallest (Krum score, client id):
+    the score of row i is the sum of its k = clamp(n − f − 2, 1, n − 1) smallest D[i, j], j ≠ i,
+    added in ascending order in fp64 (non-finite distances count as +inf; n = 1 scores 0). n < 2f + 3
+    falls back to f = max(0, (n − 3) // 2) with a warning; m is clamped to [1, n]. D is copied to
+    the host and the same code runs for both backends (`ops.ref.krum_select`)."""
+    return ref.krum_select(D, f, m, ids)
+
+
+def krum_scores(D, f: int):
+    """(fp64 [n] Krum scores on the host, the f actually used): see `krum_select`."""
+    return ref.krum_scores(D, f)
 
 
 def mix_rows(x, w, out_dtype):

@@ -1600,6 +1600,43 @@ def trimmed_sum(x, b: int, out=None):
     return out
 
 
+_pair_cache: dict = {}  # fp64 span-sum scratch of pairwise_sq_dists per (device, stream); grown, never shrunk
+
+
+def pairwise_scratch_doubles(n: int, P: int, spans_per_wg: int | None = None) -> int:
+    """Doubles of scratch a pairwise_sq_dists launch of this shape writes (all of them)."""
+    spw = int(spans_per_wg) if spans_per_wg else _C.pairwise_spans_per_wg(n, P)
+    return int(_C.pairwise_ws_doubles(n, P, spw))
+
+
+def pairwise_sq_dists(x, out=None, scratch=None, spans_per_wg: int | None = None):
+    """csrc/krum.hip: fp64 [n, n] squared L2 distances between the rows of x [n, P] in the summation
+    order of `ops.ref.pairwise_sq_dists` (spans of ref.PAIR_SPAN columns, groups of ref.PAIR_GROUP
+    spans). `scratch` (fp64, ≥ pairwise_scratch_doubles) replaces the cached span-sum buffer;
+    `spans_per_wg` (1 or ref.PAIR_GROUP; default by scratch size) is how many spans one workgroup
+    adds up itself — it never changes a bit of the result."""
+    n, P, ld = _row_args(x)
+    ref.check_pairs(n)
+    _check(x, F32, contiguous=False, name="x")
+    assert ld % 4 == 0 and x.data_ptr() % 16 == 0, "x: rows must be 16-B aligned"
+    spw = int(spans_per_wg) if spans_per_wg else _C.pairwise_spans_per_wg(n, P)
+    assert spw in (1, ref.PAIR_GROUP), spw
+    need = int(_C.pairwise_ws_doubles(n, P, spw))
+    if scratch is None:
+        key = (x.device, torch.cuda.current_stream().cuda_stream)
+        scratch = _pair_cache.get(key)
+        if scratch is None or scratch.numel() < need:
+            scratch = _pair_cache[key] = torch.empty(need, dtype=torch.float64, device=x.device)
+    _check(scratch, torch.float64, name="scratch")
+    assert scratch.numel() >= need and scratch.data_ptr() % 16 == 0
+    if out is None:
+        out = torch.empty((n, n), dtype=torch.float64, device=x.device)
+    _check(out, torch.float64, name="out")
+    assert out.shape == (n, n)
+    _C.pairwise_sq_dists(_p(x), ld, n, P, _p(scratch), spw, _p(out), _s())
+    return out
+
+
 def mix_rows(x, w, out_dtype=BF16):
     """[M, P] = W[M, K] · x[K, P]: subset models for Shapley utilities, emitted in the eval
     compute dtype (bf16 or fp32) by one native pass that reads each x row once per 32 models;

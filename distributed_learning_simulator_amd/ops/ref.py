@@ -29,9 +29,15 @@ def _match(w, K: int):
 
 
 # ----------------------------------------------------------------------------- conv
+# A client's bits must not depend on who shares its cohort (N ranks ≡ 1 rank), so torch has to pick
+# the same convolution kernels for every K. Two things stood in the way. Left to `reshape`, a lone
+# client's input (K = 1) and a contiguous weight come out as channels-last VIEWS, a cohort's input
+# and a weight that is a strided view of θ as NCHW copies: both operands are now always contiguous
+# NCHW copies. And groups = 1 takes other kernels than groups > 1: a lone client is run as two
+# identical groups (`_twice`) and the first is kept.
 def _to_grouped(x: torch.Tensor) -> torch.Tensor:
     K, B, H, W, C = x.shape
-    return x.permute(1, 0, 4, 2, 3).reshape(B, K * C, H, W)
+    return x.permute(1, 0, 4, 2, 3).reshape(B, K * C, H, W).contiguous()
 
 
 def _from_grouped(y: torch.Tensor, K: int) -> torch.Tensor:
@@ -41,11 +47,17 @@ def _from_grouped(y: torch.Tensor, K: int) -> torch.Tensor:
 
 def _w_grouped(w: torch.Tensor) -> torch.Tensor:
     K, Co, kh, kw, Ci = w.shape
-    return w.permute(0, 1, 4, 2, 3).reshape(K * Co, Ci, kh, kw)
+    return w.permute(0, 1, 4, 2, 3).reshape(K * Co, Ci, kh, kw).contiguous()
+
+
+def _twice(t):
+    return torch.cat([t, t])
 
 
 def conv_fwd(x, w, stride: int, pad: int, bias=None):
     K = x.shape[0]
+    if K == 1:
+        return conv_fwd(_twice(x), w, stride, pad, bias)[:1]
     w = _match(w, K)
     b = _match(bias, K).reshape(-1).to(x.dtype) if bias is not None else None
     y = F.conv2d(_to_grouped(x), _w_grouped(w).to(x.dtype), b, stride=stride, padding=pad, groups=K)
@@ -54,6 +66,9 @@ def conv_fwd(x, w, stride: int, pad: int, bias=None):
 
 def conv_dgrad(dy, w, in_hw, stride: int, pad: int, acc=None):
     K, B = dy.shape[:2]
+    if K == 1:
+        dx = conv_dgrad(_twice(dy), w, in_hw, stride, pad)[:1]
+        return dx if acc is None else dx + acc.to(dx.dtype)
     w = _match(w, K)
     Ci = w.shape[-1]
     dx = torch.nn.grad.conv2d_input(
@@ -66,6 +81,8 @@ def conv_dgrad(dy, w, in_hw, stride: int, pad: int, acc=None):
 
 def conv_wgrad(dy, x, w_shape, stride: int, pad: int):
     K = x.shape[0]
+    if K == 1:
+        return conv_wgrad(_twice(dy), _twice(x), w_shape, stride, pad)[:1]
     _, Co, kh, kw, Ci = w_shape
     dw = torch.nn.grad.conv2d_weight(
         _to_grouped(x), (K * Co, Ci, kh, kw), _to_grouped(dy),
@@ -465,6 +482,113 @@ def trimmed_sum(x, b, out=None):
     assert out.dtype == torch.float64 and out.dim() == 1 and out.numel() >= P
     out[:P].copy_(acc)
     return out
+
+
+PAIR_SPAN = 4096  # W: columns per span of pairwise_sq_dists (csrc/dls.h)
+PAIR_GROUP = 8  # G: consecutive spans per group
+
+
+def check_pairs(n: int) -> None:
+    if not 1 <= n <= TRIM_MAX_ROWS:
+        raise ValueError(f"pairwise_sq_dists supports 1 to {TRIM_MAX_ROWS} rows, got {n}")
+
+
+def pairwise_sq_dists(x, out=None):
+    """Squared L2 distances between the rows of x [n, P] fp32 (the oracle of csrc/krum.hip, and the
+    CPU path): fp64 [n, n] (written into `out` if given).
+
+    term(i, j, p) = fl64(d · d) with d = fl64(double(x[i, p]) − double(x[j, p])); the multiply and the
+    add that follows are rounded separately (no FMA); denormal inputs are not flushed. D[i, j] adds
+    the terms in an order fixed by the column index alone: the columns are cut into spans of W =
+    PAIR_SPAN = 4096 columns (the last may be shorter) and the spans into groups of G = PAIR_GROUP = 8
+    consecutive spans;
+      span sum  = the span's terms added one at a time in ascending column order from +0.0,
+      group sum = the group's span sums added in ascending span order from +0.0,
+      D[i, j]   = the group sums added in ascending group order from +0.0.
+    Nothing depends on n, the row order or the device: D[i, i] is +0.0 for a finite row, D[i, j] and
+    D[j, i] have the same bits, a row permutation permutes D, zero columns change nothing, D is finite
+    where both rows are, NaN / ±inf follow IEEE (NaN payload bits are not part of the contract).
+    1 ≤ n ≤ 512, else ValueError.
+
+    The loops below run over the position inside a span (all spans at once), then over the span
+    inside a group, then over the groups: plain tensor adds, no `sum` / `cumsum`."""
+    n, P = x.shape
+    check_pairs(n)
+    assert x.dtype == torch.float32
+    W, G = PAIR_SPAN, PAIR_GROUP
+    xd = x.double()
+    full, tail = P // W, P % W
+    sums = torch.zeros((full + (1 if tail else 0), n, n), dtype=torch.float64, device=x.device)  # per span
+    d = torch.empty((max(full, 1), n, n), dtype=torch.float64, device=x.device)
+    if full:
+        cols = xd[:, : full * W].reshape(n, full, W).permute(2, 1, 0).contiguous()  # [W, span, row]
+        acc = sums[:full]
+        for c in range(W):
+            torch.sub(cols[c][:, :, None], cols[c][:, None, :], out=d[:full])
+            d[:full].mul_(d[:full])
+            acc.add_(d[:full])
+    if tail:
+        cols = xd[:, full * W :].t().contiguous()  # [tail, row]
+        acc = sums[full]
+        for c in range(tail):
+            torch.sub(cols[c][:, None], cols[c][None, :], out=d[0])
+            d[0].mul_(d[0])
+            acc.add_(d[0])
+    res = torch.zeros((n, n), dtype=torch.float64, device=x.device)
+    for g0 in range(0, sums.shape[0], G):
+        group = torch.zeros((n, n), dtype=torch.float64, device=x.device)
+        for s in range(g0, min(g0 + G, sums.shape[0])):
+            group = group + sums[s]
+        res = res + group
+    if out is None:
+        return res
+    assert out.dtype == torch.float64 and out.shape == (n, n)
+    out.copy_(res)
+    return out
+
+
+def krum_scores(D, f: int):
+    """(scores [n] fp64, f actually used): the Krum score of row i is the sum of its k = clamp(n − f −
+    2, 1, n − 1) smallest D[i, j], j ≠ i, added in ascending order in fp64 from +0.0; a non-finite
+    distance counts as +inf; n = 1 scores 0. If n < 2f + 3 (a round shrunk by failures) f is replaced
+    by max(0, (n − 3) // 2), with a warning."""
+    D = D.detach().to("cpu", torch.float64)
+    n = D.shape[0]
+    assert D.shape == (n, n)
+    f = max(0, int(f))
+    if n < 2 * f + 3:
+        from ..utils.logging import get_logger
+
+        f2 = max(0, (n - 3) // 2)
+        if f2 != f:
+            get_logger().warning("krum: %d uploads cannot carry f = %d (needs n >= 2f + 3): using f = %d", n, f, f2)
+        f = f2
+    if n == 1:
+        return torch.zeros(1, dtype=torch.float64), f
+    k = min(max(n - f - 2, 1), n - 1)
+    inf = torch.tensor(float("inf"), dtype=torch.float64)
+    d = torch.where(torch.isfinite(D), D, inf)
+    off = d[~torch.eye(n, dtype=torch.bool)].reshape(n, n - 1)  # row i without D[i, i]
+    srt = torch.sort(off, dim=1).values
+    scores = torch.zeros(n, dtype=torch.float64)
+    for c in range(k):
+        scores = scores + srt[:, c]
+    return scores, f
+
+
+def krum_select(D, f: int, m: int, ids) -> list:
+    """Row indices of the m uploads with the smallest (Krum score, client id), sorted by client id.
+    `ids[i]` is the client id of row i (the tie-break, so the choice does not depend on which rank or
+    wave hosts a client); m is clamped to [1, n]. Scores: `krum_scores`. Runs on the host for both
+    backends, so a bitwise-equal D gives an identical selection."""
+    scores, _ = krum_scores(D, f)
+    n = scores.numel()
+    ids = [int(c) for c in ids]
+    assert len(ids) == n and len(set(ids)) == n, "one distinct client id per row"
+    m = min(max(int(m), 1), n)
+    sc = scores.tolist()
+    order = sorted(range(n), key=lambda i: (sc[i], ids[i]))[:m]
+    return sorted(order, key=lambda i: ids[i])
 
 
 def mix_rows(x, w, out_dtype=torch.float32):

@@ -28,5 +28,10 @@ $S --config-name fed_trimmed_mean/mnist.yaml ++fed_trimmed_mean.round=1 ++fed_tr
    ++fed_trimmed_mean.algorithm_kwargs.byzantine_number=1 ++fed_trimmed_mean.debug=True
 $S --config-name fed_median/mnist.yaml ++fed_median.round=1 ++fed_median.epoch=1 ++fed_median.worker_number=5 \
    ++fed_median.algorithm_kwargs.byzantine_number=1 ++fed_median.algorithm_kwargs.byzantine_attack=nan ++fed_median.debug=True
+# Krum / Multi-Krum (whole uploads chosen by their pairwise distances) with Byzantine clients
+$S --config-name fed_krum/mnist.yaml ++fed_krum.round=1 ++fed_krum.epoch=1 ++fed_krum.worker_number=5 \
+   ++fed_krum.algorithm_kwargs.byzantine_number=1 ++fed_krum.debug=True
+$S --config-name fed_multi_krum/mnist.yaml ++fed_multi_krum.round=1 ++fed_multi_krum.epoch=1 ++fed_multi_krum.worker_number=5 \
+   ++fed_multi_krum.algorithm_kwargs.byzantine_number=1 ++fed_multi_krum.algorithm_kwargs.byzantine_attack=nan ++fed_multi_krum.debug=True
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
