@@ -530,7 +530,11 @@ __global__ void seg_minmax_kernel(const float* __restrict__ x, const int* __rest
   }
   const int sprev = __shfl_up(s, 1, 64);
   if (s >= 0 && (lane == 0 || sprev != s)) {
-    // float atomics on min/max via int ordering trick
+    // float atomics on min/max via int ordering trick. −0.0 + 0.0 = +0.0: the bits of −0.0 are
+    // INT_MIN, which as a "non-negative" value would lose every signed max (a segment of −0.0
+    // kept −inf) and win every signed min, over negative values too
+    lo += 0.f;
+    hi += 0.f;
     float* pmn = &mn[(long)k * nseg + s];
     float* pmx = &mx[(long)k * nseg + s];
     int* imn = reinterpret_cast<int*>(pmn);

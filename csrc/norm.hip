@@ -559,16 +559,16 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const T* __restrict__ x, co
   if (row >= nrows) return;
   const int k = (int)(row / rpc);
   const T* xr = x + row * C;
+  // two passes (the row stays in cache): Σ(x − μ)², not Σx²/C − μ², whose fp32 cancellation
+  // costs (μ/σ)² in relative error on rows with an offset (3e-4 in y at μ = 64, σ = 1)
   float s = 0.f, sq = 0.f;
+  for (int c = lane; c < C; c += 64) s += ldf(xr + c);
+  const float mu = wave_sum(s) / C;
   for (int c = lane; c < C; c += 64) {
-    const float v = ldf(xr + c);
-    s += v;
-    sq += v * v;
+    const float d = ldf(xr + c) - mu;
+    sq += d * d;
   }
-  s = wave_sum(s);
-  sq = wave_sum(sq);
-  const float mu = s / C;
-  const float rs = rsqrtf(fmaxf(sq / C - mu * mu, 0.f) + eps);
+  const float rs = rsqrtf(wave_sum(sq) / C + eps);
   const T* g = gamma + (long)(k / rep) * g_cs;
   const T* b = beta + (long)(k / rep) * g_cs;
   bf16_t* hp = yp ? yp + (row + (long)k * rpc) * C : nullptr;  // (row = k·rpc + r: hi at (2k·rpc + r)·C)
@@ -610,13 +610,16 @@ __global__ void __launch_bounds__(256) ln_fwd_pairs_kernel(const float* __restri
     v[i] = xr[lane + 64 * i];
     s += v[i].x;
     s += v[i].y;
-    sq += v[i].x * v[i].x;
-    sq += v[i].y * v[i].y;
   }
-  s = wave_sum(s);
-  sq = wave_sum(sq);
-  const float mu = s / C;
-  const float rs = rsqrtf(fmaxf(sq / C - mu * mu, 0.f) + eps);
+  const float mu = wave_sum(s) / C;
+  // second pass over the registers: Σ(x − μ)² (see ln_fwd_kernel)
+#pragma unroll
+  for (int i = 0; i < NC2; ++i) {
+    const float dx = v[i].x - mu, dy = v[i].y - mu;
+    sq += dx * dx;
+    sq += dy * dy;
+  }
+  const float rs = rsqrtf(wave_sum(sq) / C + eps);
   const float2* g = reinterpret_cast<const float2*>(gamma + (long)(k / rep) * g_cs);
   const float2* b = reinterpret_cast<const float2*>(beta + (long)(k / rep) * g_cs);
   float2* yr = reinterpret_cast<float2*>(y + row * C);
