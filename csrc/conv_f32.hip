@@ -410,8 +410,13 @@ int vw(int c) { return (c % 8 == 0) ? 8 : (c % 4 == 0) ? 4 : 1; }
 // without, 757 / 765 ms with the NT / wgrad rule — removed)
 
 // --------------------------------------------------------------------------- TN (wgrad)
-template <int BMc, int BNr, int BKT, int WM, int WN, int VA, int VB, int NBUF>
+// BNB (ConvTNParams::bnb_*): dY is the input gradient of a BatchNorm(+ReLU) that was never written —
+// the A loader fetches the BN's output gradient, its input and the ReLU bits and forms
+// dX = a·(dy·bit) + (e·x + d), bn_bwd_apply_kernel's expression (norm.hip), before the split; rows
+// past the client's valid rows are zeros, as that pass writes them
+template <int BMc, int BNr, int BKT, int WM, int WN, int VA, int VB, int NBUF, bool BNB = false>
 __global__ void __launch_bounds__(WM* WN * 64) conv_tn_f32_kernel(ConvTNParams p) {
+  static_assert(!BNB || VA == 8, "the BN-backward loader reads one ReLU mask byte per 8 channels");
   constexpr int T = WM * WN * 64;
   constexpr int TM = BMc / (WM * 32), TN = BNr / (WN * 32);
   constexpr int LDA = BMc + 32;
@@ -463,6 +468,27 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_tn_f32_kernel(ConvTNParams p
   const auto xr = make_rsrc(x, (uint32_t)((long)p.B * p.H * p.W * p.ldx * 4));
   const bool a_live = cok && !(A_PART && tid / CCA >= BKT);
   int k_next = mbeg;
+  // BN-backward loader: the thread's channel group is fixed, so are its (a, d, e) coefficients
+  constexpr int PAB = BNB ? PA : 1, VAB = BNB ? VA : 1;
+  FV<VAB> rxa[PAB];
+  uint32_t rbits[PAB];
+  bool rlive[PAB];
+  float bn_a[VAB], bn_d[VAB], bn_e[VAB];
+  const auto xbr = make_rsrc(BNB ? p.bnb_x + (long)client * p.dy_cs : reinterpret_cast<const float*>(p.dy),
+                             BNB ? (uint32_t)((long)p.M * p.ldy * 4) : 0u);
+  const uint8_t* __restrict__ bn_mask = nullptr;
+  int a_mend = mend;  // rows of this split that carry a gradient (BNB: the client's valid rows)
+  if constexpr (BNB) {
+#pragma unroll
+    for (int i = 0; i < VA; ++i) {
+      const long q = 3 * ((long)client * p.Co + (cok ? cocol + i : 0));
+      bn_a[i] = p.bnb_coef[q];
+      bn_d[i] = p.bnb_coef[q + 1];
+      bn_e[i] = p.bnb_coef[q + 2];
+    }
+    if (p.bnb_mask) bn_mask = p.bnb_mask + ((long)client * p.M * p.Co >> 3);
+    if (p.bnb_valid) a_mend = min(mend, p.bnb_valid[client]);
+  }
   // im2col rows of X̃ without divisions in the loop: each of the thread's PB GEMM rows m keeps
   // its input coordinates (ih, iw) and element offset, advanced by BKT rows per step through the
   // fixed decomposition BKT = q_b·OH·OW + q_oh·OW + r_ow (one carry per level: no muls)
@@ -495,7 +521,16 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_tn_f32_kernel(ConvTNParams p
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
       const int m = k0 + tid / CCA + j * RPA;
-      buf_load<VA>(ra[j].v, dyr, (a_live && m < mend) ? (uint32_t)(a_off + j * a_jstep) * 4u : OOB_OFF);
+      if constexpr (BNB) {
+        const bool live = a_live && m < a_mend;
+        const uint32_t off = live ? (uint32_t)(a_off + j * a_jstep) * 4u : OOB_OFF;
+        buf_load<VA>(ra[j].v, dyr, off);
+        buf_load<VA>(rxa[j].v, xbr, off);
+        rbits[j] = (bn_mask && live) ? bn_mask[(a_off + j * a_jstep) >> 3] : 0xFFu;
+        rlive[j] = live;
+      } else {
+        buf_load<VA>(ra[j].v, dyr, (a_live && m < mend) ? (uint32_t)(a_off + j * a_jstep) * 4u : OOB_OFF);
+      }
     }
     a_off += a_kstep;
 #pragma unroll
@@ -524,6 +559,14 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_tn_f32_kernel(ConvTNParams p
     for (int j = 0; j < PA; ++j) {
       if (A_PART && tid / CCA >= BKT) continue;
       const int off = (buf * BKT + tid / CCA + j * RPA) * LDA + ca * VA;
+      if constexpr (BNB) {
+#pragma unroll
+        for (int i = 0; i < VA; ++i) {
+          const float g = ((rbits[j] >> i) & 1u) ? ra[j].v[i] : 0.f;
+          const float o = fmaf(bn_a[i], g, fmaf(bn_e[i], rxa[j].v[i], bn_d[i]));
+          ra[j].v[i] = rlive[j] ? o : 0.f;
+        }
+      }
       st_split(As + off, As + A_PLANE + off, ra[j]);
     }
 #pragma unroll
@@ -624,6 +667,15 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_tn_f32_kernel(ConvTNParams p
   }
 }
 
+// the BN-backward loader (ConvTNParams::bnb_coef): 8-wide vectors, the tiles of Co <= 64
+template <int BMc, int BNr, int BKT, int WM, int WN, int NBUF>
+bool launch_tn_f32_bnb(const ConvTNParams& p, int va, int vb, int grid, hipStream_t s) {
+  if (va != 8 || vb != 8) return false;
+  hipLaunchKernelGGL((conv_tn_f32_kernel<BMc, BNr, BKT, WM, WN, 8, 8, NBUF, true>), dim3(grid), dim3(WM * WN * 64), 0,
+                     s, p);
+  return true;
+}
+
 template <int BMc, int BNr, int BKT, int WM, int WN, int NBUF, bool ALLV>
 bool launch_tn_f32_cfg(const ConvTNParams& p, int va, int vb, int grid, hipStream_t s) {
 #define TNF_CASE(A, B)                                                                                          \
@@ -649,7 +701,17 @@ constexpr TnTile kTnF32Tiles[] = {{128, 128}, {64, 128}, {128, 128}, {256, 128},
 constexpr int kTnF32Variants = sizeof(kTnF32Tiles) / sizeof(kTnF32Tiles[0]);
 constexpr int TN_BKT_MAX = 32;
 
+// the variants with a BN-backward instantiation: what tn_f32_default_variant selects for Co = 64
+bool tn_f32_bnb_variant(int v) { return v == 1 || v == 5; }
+
 bool launch_tn_f32_variant(int v, const ConvTNParams& p, int va, int vb, int grid, hipStream_t s) {
+  if (p.bnb_coef) {
+    switch (v) {
+      case 1: return launch_tn_f32_bnb<64, 128, 32, 2, 2, 2>(p, va, vb, grid, s);
+      case 5: return launch_tn_f32_bnb<64, 64, 32, 2, 2, 2>(p, va, vb, grid, s);
+      default: return false;
+    }
+  }
   switch (v) {
     case 0: return launch_tn_f32_cfg<128, 128, 32, 2, 2, 2, true>(p, va, vb, grid, s);  // 80 KB
     case 1: return launch_tn_f32_cfg<64, 128, 32, 2, 2, 2, true>(p, va, vb, grid, s);   // 60 KB
@@ -799,12 +861,24 @@ void conv_tn_f32(ConvTNParams p, int K, int variant, hipStream_t s) {
   const int va = vw(std::gcd(p.Co, p.ldy));
   const int vb = vw(std::gcd(p.C, p.ldx));
   variant = resolve_tn_f32_variant(variant, K, p.Co, p.R, va, vb);
+  if (p.bnb_coef && !(p.bnb_x && p.ldy == p.Co && p.dy_cs == (long)p.M * p.Co && va == 8 && vb == 8 &&
+                      tn_f32_bnb_variant(variant))) {
+    // (callers ask conv_tn_f32_bn_bwd_ok first)
+    fprintf(stderr, "conv_tn_f32: the BN-backward loader does not serve this launch (Co %d, C %d, variant %d)\n",
+            p.Co, p.C, variant);
+    abort();
+  }
   tn_f32_split(K, p.Co, p.R, p.M, variant, p.splitk, p.m_per_split);
   const TnTile t = kTnF32Tiles[variant];
   const long tiles = (long)K * cdiv(p.Co, t.bm) * cdiv(p.R, t.bn);
   const int grid = (int)(tiles * p.splitk);
   if (!launch_tn_f32_variant(variant, p, va, vb, grid, s)) fprintf(stderr, "conv_tn_f32: bad variant %d\n", variant);
   if (p.splitk > 1 && p.part != nullptr) tn_fold(p.part, p.dw, p.dw_cs, K, p.splitk, (long)p.Co * p.R, s);
+}
+
+bool conv_tn_f32_bn_bwd_ok(int K, int Co, int R, int gco, int gc, int variant) {
+  const int va = vw(gco), vb = vw(gc);
+  return va == 8 && vb == 8 && tn_f32_bnb_variant(resolve_tn_f32_variant(variant, K, Co, R, va, vb));
 }
 
 // gco / gc: the channel counts' gcd with their row strides (they set the vector widths)

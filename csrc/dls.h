@@ -298,6 +298,15 @@ struct ConvTNParams {
   // (conv_pl.hip, set by conv_tn_pl for small images) the pixel reduction walks (pixel, 32-image
   // chunk) pairs over only the pixels the workgroup's tap lands inside the image for
   int pix;
+  // (conv_f32.hip, fp32 operands only; optional) dy is the OUTPUT gradient of a BatchNorm(+ReLU)
+  // whose input gradient is this GEMM's A operand: the loader applies the BN backward, dX = a·(dy·
+  // relu') + e·x + d. bnb_x: the BN input [K][M][Co] fp32 (dy's strides, ldy = Co); bnb_mask: the
+  // ReLU bits [K][M][Co/8] or null (no ReLU); bnb_coef [K][Co][3] = (a, d, e), set = mode on;
+  // bnb_valid [K] or null: rows m >= bnb_valid[k] are zeros
+  const float* bnb_x;
+  const uint8_t* bnb_mask;
+  const float* bnb_coef;
+  const int* bnb_valid;
 };
 
 // Large-tile conv GEMM fed by the LDS-DMA (conv_gl.hip): K loop over a tap table × 64-channel
@@ -434,6 +443,8 @@ void tn_fold(const float* part, float* dw, long dw_cs, int K, int splitk, long C
              const SgdEpi* sgd = nullptr);
 int conv_tn_f32_num_variants();
 int conv_tn_f32_splitk(int K, int Co, int R, int M, int gco, int gc, int variant);
+// whether conv_tn_f32 has a BN-backward loader (ConvTNParams::bnb_coef) for the variant the launch resolves to
+bool conv_tn_f32_bn_bwd_ok(int K, int Co, int R, int gco, int gc, int variant);
 
 // ---------------------------------------------------------------- normalisation
 // Activation / γ / β pointers are the compute dtype: bf16 (f32 = 0) or fp32 (f32 = 1, the
@@ -445,7 +456,8 @@ void bn_fwd(const void* x, const void* gamma, const void* beta, const void* res,
             int ldx = 0, const float* pre_part = nullptr,
             int pre_nparts = 0, bf16_t* yp = nullptr,
             int y_f32 = 1, float* coef_out = nullptr, int apply = 1,
-            const float* res_coef = nullptr);  // res_coef [K][C][2]: res is a second BN's raw input, applied here; yp / y_f32: split planes of y (fp32 only) with or without y; relu_mask: optional [K][R][C/8] bits out; ldx: row stride of x / res (channel slice of a wider buffer), y
+            const float* res_coef = nullptr,
+            int res_relu = 0);  // res_coef [K][C][2]: res is a second BN's raw input, applied here (res_relu: with its ReLU); yp / y_f32: split planes of y (fp32 only) with or without y; relu_mask: optional [K][R][C/8] bits out; ldx: row stride of x / res (channel slice of a wider buffer), y
                                   // contiguous; pre_part: [K][pre_nparts][2C] Σx / Σx² partials from the
                                   // producing conv's epilogue (ConvNTParams::stats) — no statistics pass
 void bn_bwd(const void* dy, const void* x, const void* y, const float* mean, const float* rstd, const void* gamma,

@@ -403,10 +403,12 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
                                                        const float* __restrict__ coef, int R, int C, int relu,
                                                        int rpb, uint8_t* __restrict__ rmask, int ldx,
                                                        bf16_t* __restrict__ yp, int y_f32,
-                                                       const float* __restrict__ res_coef) {
+                                                       const float* __restrict__ res_coef, int res_relu) {
   // x / res rows at stride ldx (channel slice of a wider buffer), y contiguous. res_coef [K][C][2]:
-  // res is the RAW input of a second BatchNorm (no ReLU, same valid rows) whose apply is folded
-  // in here — out += res_scale·res + res_shift, the bits of applying it first (ResNet downsample)
+  // res is the RAW input of a second BatchNorm (same valid rows) whose apply is folded in here —
+  // out += res_scale·res + res_shift, the bits of applying it first (ResNet downsample); res_relu:
+  // that BatchNorm has a ReLU (the ResNet stem, read as layer1.0's identity shortcut): out +=
+  // max(res_scale·res + res_shift, 0), what its own apply would have stored as fp32
   const int k = blockIdx.y;
   const int CT = C / V;
   const int nvalid = valid_rows ? min(valid_rows[k], R) : R;
@@ -438,7 +440,10 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
         if (res) {
           float rv[V];
           load_vec<V>(res + offx, rv);
-          if (res_coef) {
+          if (res_coef && res_relu) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) out[j] += fmaxf(fmaf(rv[j], rsc[j], rsh[j]), 0.f);
+          } else if (res_coef) {
 #pragma unroll
             for (int j = 0; j < V; ++j) out[j] += fmaf(rv[j], rsc[j], rsh[j]);
           } else {
@@ -783,7 +788,8 @@ long bn_workspace_floats(int K, long R, int C) {
 void bn_fwd(const void* x, const void* gamma, const void* beta, const void* res, void* y, float* mean, float* rstd,
             const int* valid_rows, long g_cs, int K, int R, int C, int relu, float eps, int rep, float* ws,
             uint8_t* rmask, int f32, hipStream_t s, int ldx, const float* pre_part,
-            int pre_nparts, bf16_t* yp, int y_f32, float* coef_out, int apply, const float* res_coef) {
+            int pre_nparts, bf16_t* yp, int y_f32, float* coef_out, int apply, const float* res_coef,
+            int res_relu) {
   if (ldx == 0) ldx = C;
   // ws layout: [K][3C] coefficients, then [K][parts][2C] per-workgroup partial sums. coef_out: the
   // (scale, shift) pairs go there instead and outlive this call (apply = 0: the consumer conv
@@ -818,7 +824,7 @@ void bn_fwd(const void* x, const void* gamma, const void* beta, const void* res,
     if (apply) {
       DISPATCH_V(V, hipLaunchKernelGGL((bn_apply_kernel<TT, VV>), grid, dim3(256), 0, s, CP(x), CP(res), MP(y),
                                        valid_rows, coef, R, C, relu, rpb, rmask, ldx, f32 ? yp : nullptr,
-                                       f32 ? y_f32 : 1, res_coef));
+                                       f32 ? y_f32 : 1, res_coef, res_relu));
     }
   });
 }
@@ -831,10 +837,11 @@ void bn_apply_only(const float* x, const float* coef, const int* valid_rows, int
   dim3 grid(cdiv(R, rpb), K);
   if (C % 8 == 0) {
     hipLaunchKernelGGL((bn_apply_kernel<float, 8>), grid, dim3(256), 0, s, x, (const float*)nullptr, y,
-                       valid_rows, coef, R, C, relu, rpb, rmask, C, yp, y ? 1 : 0, (const float*)nullptr);
+                       valid_rows, coef, R, C, relu, rpb, rmask, C, yp, y ? 1 : 0, (const float*)nullptr, 0);
   } else {
     hipLaunchKernelGGL((bn_apply_kernel<float, 1>), grid, dim3(256), 0, s, x, (const float*)nullptr, y,
-                       valid_rows, coef, R, C, relu, rpb, (uint8_t*)nullptr, C, yp, y ? 1 : 0, (const float*)nullptr);
+                       valid_rows, coef, R, C, relu, rpb, (uint8_t*)nullptr, C, yp, y ? 1 : 0, (const float*)nullptr,
+                       0);
   }
 }
 

@@ -160,7 +160,8 @@ class BatchNorm(Module):
         """`planes`: the output's consumers are split-plane convs (Fn.batch_norm): 1 = they and
         fp32 readers, 2 = split-plane convs only. Effective while the weights' planes are live
         (training steps with BoundParams.split); otherwise the output is plain fp32. 4: the output
-        is read only as the next BatchNorm's residual, which folds this apply into its own."""
+        is read only as the next BatchNorm's residual, which folds this apply into its own. 5: one
+        3x3 stride-1 conv and the next BatchNorm (as its residual) read it, and apply it themselves."""
         P = ctx.P
         rps = 1
         for d in x.shape[2:-1]:

@@ -184,14 +184,19 @@ class ResNetNet(Module):
         self.child("fc", Linear(c, classes))
 
     def forward(self, x, ctx):
-        x = conv_bn(self.conv1, self.bn1, x, ctx, planes=0 if not self.cifar_stem else 1)
+        blocks = [b for s in self.stages for b in s.children]
+        # the CIFAR stem's BN output is read by the first block's conv1 (planes) and, when that block
+        # is an identity-shortcut BasicBlock, by its bn2 as the residual (fp32): both can apply the BN
+        # themselves (Fn.batch_norm planes=5). Otherwise one apply pass writes fp32 + planes
+        first = blocks[0] if blocks else None
+        two_reader = self.cifar_stem and isinstance(first, BasicBlock) and first.down is None
+        x = conv_bn(self.conv1, self.bn1, x, ctx, planes=0 if not self.cifar_stem else 5 if two_reader else 1)
         if not self.cifar_stem:
             x = self.maxpool.forward(x, ctx)
         # each block output is written in the form(s) its readers take: split planes only when a
         # downsample block follows (its convs read planes; its shortcut is a conv too), fp32 only
         # before the pooling head, both otherwise (planes for the convs, fp32 for the identity
         # shortcut's residual add)
-        blocks = [b for s in self.stages for b in s.children]
         for i, b in enumerate(blocks):
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
             op = 0 if nxt is None else 2 if nxt.down is not None else 1

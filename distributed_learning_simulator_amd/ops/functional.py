@@ -78,12 +78,15 @@ class BNStats:
     - `dy_planes_ok`: the conv runs its dgrad and wgrad on split planes (csrc/conv_pl.hip), so
       the BN backward writes only dX's planes (ops.hip.bn_bwd dx_planes=2), never the fp32 dX."""
 
-    __slots__ = ("valid", "part", "dy_planes_ok")
+    __slots__ = ("valid", "part", "dy_planes_ok", "wgrad_bn_bwd_ok")
 
     def __init__(self, valid=None):
         self.valid = valid
         self.part = None
         self.dy_planes_ok = False
+        # the conv's weight gradient is its backward's only reader of dY and can apply the BN
+        # backward in its fp32 dY loader (DeferredBNBwdF32)
+        self.wgrad_bn_bwd_ok = False
 
 
 # BN backward passes that used a dgrad's partials ("used"), whose consumer wrote none (a strided
@@ -156,6 +159,42 @@ class DeferredBN:
             self.pending = False
 
 
+# two-reader deferred BNs (DeferredStemBN): applies taken by the halo conv ("conv") or folded into
+# the next BN's residual add ("res"), and forms written by a pass of their own ("materialized")
+stem_defer_count = {"conv": 0, "res": 0, "materialized": 0}
+
+
+class DeferredStemBN(DeferredBN):
+    """A DeferredBN with a second reader: the next BatchNorm, which takes the output as its residual
+    (batch_norm planes=5: the CIFAR ResNet stem BN, read by layer1.0.conv1 and, through the identity
+    shortcut, by layer1.0.bn2). The conv side is DeferredBN's (`pending`, `materialize()`: planes +
+    ReLU bits). The residual side folds the apply into the reading BN (hip.bn_fwd res_coef +
+    res_relu: the fp32 bits this BN's own pass would have stored) or calls `materialize_f32()`, which
+    writes the fp32 form into a tensor of its own. The two readers are independent and each form is
+    written at most once. The tensor autograd carries is the planes-only alias: a reader that knows
+    neither side fails (_require_fp32)."""
+
+    __slots__ = ("y32",)
+
+    def __init__(self, x, coef, relu, valid_rows, yp, mask, write_out):
+        super().__init__(x, coef, relu, valid_rows, yp, mask, write_out)
+        self.y32 = None
+
+    def materialize(self):
+        if self.pending:
+            stem_defer_count["materialized"] += 1
+        super().materialize()
+
+    def materialize_f32(self):
+        if self.y32 is None:
+            from . import hip
+
+            self.y32 = torch.empty(self.x.shape, dtype=self.x.dtype, device=self.x.device)
+            hip.bn_apply_only(self.x, self.coef, self.valid_rows, self.relu, None, y=self.y32)
+            stem_defer_count["materialized"] += 1
+        return self.y32
+
+
 # downsample BN applies folded into the next BN ("folded") or run as their own pass ("materialized")
 res_fold_count = {"folded": 0, "materialized": 0}
 
@@ -215,6 +254,42 @@ class DeferredBNBwd:
         return (self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dxp)
 
 
+# deferred BN backward applies (DeferredBNBwdF32) taken by an fp32 weight gradient's loader
+# ("wgrad") or run as their own pass ("materialized"): tests, reports
+bn_bwd_f32_defer_count = {"wgrad": 0, "materialized": 0}
+
+
+class DeferredBNBwdF32:
+    """A training BatchNorm's input gradient dX whose apply pass is deferred to the conv that
+    produced the BN's input, when that conv's backward is a weight gradient alone (its input needs no
+    gradient: the ResNet stem; OPTIONS.bn_bwd_in_wgrad_f32). The BN backward computed only its
+    coefficients (a, d, e) and dγ / dβ and hands autograd the unwritten fp32 tensor `dx`, tagged
+    unreadable (_require_fp32). The conv's fp32 TN weight gradient builds dX = a·(dy·relu') + e·x + d
+    in its dY loader (ops.hip.conv_wgrad bn_bwd=); any other consumer calls `materialize()` — the
+    ordinary apply pass into `dx`, with the same bits — which clears the tag."""
+
+    __slots__ = ("dy", "x", "mask", "coef", "valid_rows", "dx", "pending")
+
+    def __init__(self, dy, x, mask, coef, valid_rows, dx):
+        self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dx = dy, x, mask, coef, valid_rows, dx
+        self.pending = True
+
+    def materialize(self, holder=None):
+        """`holder`: the tensor autograd delivered (an alias of `dx`), whose tag is cleared too."""
+        if self.pending:
+            from . import hip
+
+            hip.bn_bwd_apply_f32(self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dx)
+            self.pending = False
+            bn_bwd_f32_defer_count["materialized"] += 1
+        for t in (self.dx, holder):
+            if t is not None:
+                t._dls_planes_only = False
+
+    def wgrad_args(self):
+        return (self.dy, self.x, self.mask, self.coef, self.valid_rows)
+
+
 class _Conv(torch.autograd.Function):
     """Conv2d over the client dim. If the input carries more channels than the weight (image
     data stored zero-padded to 8 channels), the weight is zero-padded to match and only the
@@ -257,8 +332,10 @@ class _Conv(torch.autograd.Function):
         defer = getattr(x, "_dls_bn_defer", None)
         if defer is not None and defer.pending:
             # a deferred BN input (DeferredBN): apply it in this conv's halo loader if it can
-            if (use_pl and stride == 1 and pad == 1 and KH == 3 and w.shape[3] == 3 and b is None
-                    and be.halo_bn_ok(x.shape, w)):
+            # (bn_fused_halo off: a two-reader deferral's conv side materialises; a DeferredBN is
+            # never created then)
+            if (OPTIONS.bn_fused_halo and use_pl and stride == 1 and pad == 1 and KH == 3 and w.shape[3] == 3
+                    and b is None and be.halo_bn_ok(x.shape, w)):
                 part = (torch.empty((K, be.conv_stats_parts(B * OH * OW), 2, w.shape[1]), dtype=torch.float32,
                                     device=x.device) if want_stats else None)
                 # the weight gradient applies the BN in its own loader too (halo wgrad x mode 2): then
@@ -271,6 +348,8 @@ class _Conv(torch.autograd.Function):
                                         mask=defer.mask if defer.write_out else None)
                 if y is not None:
                     defer.pending = False
+                    if isinstance(defer, DeferredStemBN):
+                        stem_defer_count["conv"] += 1
                     if want_stats:
                         stats.part = part
                     if bn_wgrad:
@@ -287,6 +366,15 @@ class _Conv(torch.autograd.Function):
             y = be.conv_fwd(x, w, stride, pad, bias=b, w_split=w_split, **pl)
         else:
             y = be.conv_fwd(x, w, stride, pad, bias=b)
+        # the backward is a weight gradient alone, on the fp32 TN kernel: the consuming BN may leave its
+        # backward's apply pass to that kernel's dY loader (DeferredBNBwdF32)
+        ctx.wgrad_bn_bwd = bool(
+            OPTIONS.bn_bwd_in_wgrad_f32 and stats is not None and be is not ref and x.dtype == torch.float32
+            and not ctx.needs_input_grad[0] and link is None and donor is None and b is None and gw is not None
+            and not use_pl and not big and w.shape[1] % 8 == 0 and x.is_contiguous()
+            and be.conv_wgrad_bn_bwd_ok(x.shape, w.shape[1], KH, w.shape[3]))
+        if stats is not None:
+            stats.wgrad_bn_bwd_ok = ctx.wgrad_bn_bwd
         ctx.w_split = w_split
         # the consuming BN will hand the backward dY as planes only: a dY without them (a tensor
         # rebuilt on the way, which drops the _dls_planes attributes) must fail, not be read as fp32
@@ -313,10 +401,12 @@ class _Conv(torch.autograd.Function):
         return y
 
     @staticmethod
-    def _wgrad(ctx, dy, x, w, dyp, be, bbd=None, sgd_ok=True) -> bool:
+    def _wgrad(ctx, dy, x, w, dyp, be, bbd=None, sgd_ok=True, bbf=None) -> bool:
         """The weight gradient (or the SGD step fused into it). `bbd` (DeferredBNBwd): only the halo
         kernel's BN-backward dY mode — returns False, launching nothing, when it cannot serve;
-        `sgd_ok` False: store dW (the flat step covers the weight)."""
+        `sgd_ok` False: store dW (the flat step covers the weight). `bbf` (DeferredBNBwdF32, a
+        backward whose forward set ctx.wgrad_bn_bwd): the fp32 TN kernel's BN-backward dY loader, a
+        plain store of dW."""
         if bbd is not None:
             if not (ctx.stride == 1 and ctx.pad == 1 and w.shape[2] == 3 and w.shape[3] == 3):
                 return False
@@ -335,7 +425,9 @@ class _Conv(torch.autograd.Function):
         sgd = ctx.sgd if not padded else None
         stepped = False
         gw = torch.empty((K,) + tuple(w.shape[1:]), dtype=torch.float32, device=dy.device) if padded else ctx.gw
-        if be is ref:
+        if bbf is not None:
+            be.conv_wgrad(dy, x, gw, ctx.stride, ctx.pad, bn_bwd=bbf.wgrad_args())
+        elif be is ref:
             gw.copy_(ref.conv_wgrad(dy.float(), x.float(), (K,) + tuple(w.shape[1:]), ctx.stride, ctx.pad))
             if ctx.gb is not None:
                 ctx.gb.copy_(dy.float().sum(dim=(1, 2, 3)))
@@ -413,12 +505,24 @@ class _Conv(torch.autograd.Function):
                 bn_bwd_defer_count["wgrad"] += 1
             else:
                 bbd.materialize()
+        bbf = getattr(dy, "_dls_bnbwd_f32", None)
+        if bbf is not None and bbf.pending:
+            # dY is a deferred BN input gradient, unwritten (DeferredBNBwdF32): the fp32 weight
+            # gradient, this backward's only reader of it, applies the BN backward in its loader
+            if ctx.wgrad_bn_bwd and not ctx.needs_input_grad[0] and acc is None and dyp is None:
+                _Conv._wgrad(ctx, dy, x, w, None, be, bbf=bbf)
+                wgrad_done = True
+                bbf.pending = False
+                bn_bwd_f32_defer_count["wgrad"] += 1
+            else:
+                bbf.materialize(dy)
         if dyp is not None and ctx.xp is None:
             raise RuntimeError("conv2d backward: dY planes without the input's planes")
         if dyp is None:
             if ctx.expect_dy_planes:
                 raise RuntimeError("conv2d backward: the BN wrote dY as planes only, but they did not arrive")
-            _require_fp32(dy, "conv2d backward")
+            if not wgrad_done or ctx.needs_input_grad[0]:
+                _require_fp32(dy, "conv2d backward")
         donor = ctx.donor
         compact = (donor is not None and not donor.receiver_done and be is not ref and dy.dtype == torch.float32
                    and ctx.stride > 1 and ctx.pad == 0 and w.shape[2] == 1 and w.shape[3] == 1 and acc is None
@@ -681,14 +785,26 @@ class _BN(torch.autograd.Function):
         K = x.shape[0]
         C = x.shape[-1]
         _require_fp32(x, "batch_norm")
-        if residual is not None:
-            _require_fp32(residual, "batch_norm residual")
         x3 = x.reshape(K, -1, C)
-        r3 = residual.reshape(K, -1, C) if residual is not None else None
+        res_coef = None
+        res_relu = False
+        r3 = None
+        sdef = getattr(residual, "_dls_bn_defer", None) if residual is not None else None
+        if isinstance(sdef, DeferredStemBN):
+            # the residual is a two-reader deferred BN output: its apply is folded into this one, or
+            # its fp32 form is written first (the tensor itself holds planes, or nothing)
+            if (be is not ref and x.dtype == torch.float32 and sdef.y32 is None and sdef.valid_rows is valid_rows
+                    and sdef.x.shape == x3.shape and x3.is_contiguous() and sdef.x.is_contiguous()):
+                r3, res_coef, res_relu = sdef.x, sdef.coef, sdef.relu
+                stem_defer_count["res"] += 1
+            else:
+                r3 = sdef.materialize_f32().reshape(K, -1, C)
+        elif residual is not None:
+            _require_fp32(residual, "batch_norm residual")
+            r3 = residual.reshape(K, -1, C)
         mask = None
         yp = None
         bnb = None
-        res_coef = None
         fold = getattr(residual, "_dls_res_fold", None) if residual is not None else None
         if fold is not None and fold.pending:
             # a downsample BN's apply folded into this one (DeferredRes), or materialised first
@@ -714,6 +830,8 @@ class _BN(torch.autograd.Function):
                 planes = 2  # (no deferral: apply now, planes only)
             if planes == 4 and not (OPTIONS.bn_res_fold and residual is None and not relu and x3.is_contiguous()):
                 planes = 0  # (no fold: apply now, fp32)
+            if planes == 5 and not (OPTIONS.bn_stem_defer and residual is None and C8 and x3.is_contiguous()):
+                planes = 1  # (no deferral: apply now, fp32 + planes)
             if planes == 4:
                 # the reader (the next BN, as its residual) applies it (DeferredRes)
                 coef, mean, rstd = be.bn_coef(x3, gamma, beta, valid_rows, pre_stats=pre)
@@ -721,17 +839,19 @@ class _BN(torch.autograd.Function):
                 fold_out = DeferredRes(x3, coef, valid_rows, y)
                 defer = None
                 planes = 0
-            elif planes == 3:
+            elif planes == 3 or planes == 5:
                 # deferred apply (DeferredBN): statistics + coefficients now; the consuming 3x3 conv
                 # applies them in its halo loader, or materialises the planes / ReLU bits first
+                # (5, DeferredStemBN: and the next BN, which reads the output as its residual)
                 coef, mean, rstd = be.bn_coef(x3, gamma, beta, valid_rows, pre_stats=pre)
                 y, yp = be.planes_buffer((K, x3.shape[1], C), x.device)
                 mask = torch.empty((K, x3.shape[1], C // 8), dtype=torch.uint8, device=x.device) if (wm and relu) else None
-                defer = DeferredBN(x3, coef, relu, valid_rows, yp, mask, write_out=wm)
+                defer = (DeferredBN if planes == 3 else DeferredStemBN)(x3, coef, relu, valid_rows, yp, mask,
+                                                                        write_out=wm)
             else:
                 defer = None
                 out = be.bn_fwd(x3, gamma, beta, valid_rows, relu, r3, with_mask=wm, pre_stats=pre, planes=planes,
-                                res_coef=res_coef)
+                                res_coef=res_coef, res_relu=res_relu)
                 y, mean, rstd = out[:3]
                 mask = out[3] if wm else None
                 if planes:
@@ -752,11 +872,12 @@ class _BN(torch.autograd.Function):
         ctx.bnb = bnb
         ctx.planes_on = OPTIONS.planes  # (the backward's dX-planes decision follows the forward's)
         ctx.bwd_in_wgrad = OPTIONS.bn_bwd_in_wgrad
+        ctx.bwd_in_wgrad_f32 = OPTIONS.bn_bwd_in_wgrad_f32
         yo = y.reshape(x.shape)
         if yp is not None:
             _tag_planes(yo, yp.view((K, 2) + tuple(x.shape[1:])), planes >= 2)
         ctx.defer = None
-        if be is not ref and planes == 3:
+        if be is not ref and planes in (3, 5):
             yo._dls_bn_defer = ctx.defer = defer
         if fold_out is not None:
             yo._dls_res_fold = fold_out
@@ -809,6 +930,21 @@ class _BN(torch.autograd.Function):
                 dxo._dls_bnbwd = DeferredBNBwd(dy3, x3, ctx.relu_mask if ctx.relu else None, coef, ctx.valid_rows,
                                                dxp)
                 return dxo, None, None, None, None, None, None, None, None, None, None, None
+            if (dxm == 0 and ctx.bwd_in_wgrad_f32 and ctx.stats is not None and ctx.stats.wgrad_bn_bwd_ok
+                    and not ctx.has_res and C % 8 == 0 and (ctx.relu_mask is not None or not ctx.relu)
+                    and x3.is_contiguous() and dy3.dtype == torch.float32):
+                # coefficients only: the producing conv's backward is an fp32 weight gradient alone,
+                # which applies them in its dY loader (DeferredBNBwdF32), or materialize() does
+                coef = torch.empty((K, C, 3), dtype=torch.float32, device=dy3.device)
+                be.bn_bwd(dy3, x3, y, mean, rstd, gamma, ctx.valid_rows, ctx.relu, ctx.ggamma, ctx.gbeta, False,
+                          relu_mask=ctx.relu_mask, pre_part=pre, coef_out=coef)
+                dx = torch.empty((K, R, C), dtype=torch.float32, device=dy3.device)
+                dxo = dx.reshape(ctx.shape)
+                _tag_planes(dxo, None, True)  # (unwritten: no fp32 reader may take it as it is)
+                _tag_planes(dx, None, True)
+                dxo._dls_bnbwd_f32 = DeferredBNBwdF32(dy3, x3, ctx.relu_mask if ctx.relu else None, coef,
+                                                      ctx.valid_rows, dx)
+                return dxo, None, None, None, None, None, None, None, None, None, None, None
             out = be.bn_bwd(dy3, x3, y, mean, rstd, gamma, ctx.valid_rows, ctx.relu,
                             ctx.ggamma, ctx.gbeta, ctx.has_res and not masked, relu_mask=ctx.relu_mask,
                             dx_planes=dxm, pre_part=pre)
@@ -842,7 +978,9 @@ def batch_norm(x, token, gamma, beta, ggamma, gbeta, valid_rows=None, relu=False
     split-plane convs (e.g. a ResNet block's inner BN), 3 = as 2 with the apply pass deferred to
     the ONE conv that reads it (DeferredBN: a 3x3 stride-1 halo conv applies it while staging);
     4 (no ReLU): the output's one reader is the next BatchNorm, as its residual, which folds this
-    apply into its own (DeferredRes: a ResNet downsample shortcut)."""
+    apply into its own (DeferredRes: a ResNet downsample shortcut); 5: as 3 with a second reader,
+    the next BatchNorm, which takes the output as its residual and folds this apply (with its ReLU)
+    into its own (DeferredStemBN: the CIFAR ResNet stem before an identity-shortcut block)."""
     return _BN.apply(x, token, gamma, beta, ggamma, gbeta, valid_rows, relu, residual, link, stats, planes)
 
 

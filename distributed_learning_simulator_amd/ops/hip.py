@@ -442,13 +442,57 @@ def _tn_launch(dy, x, gw, dy_cs, x_cs, B, H, W, C, OH, OW, KH, KW, stride, pad, 
                f32, _s(), ldy, ldx, part, dy_lo, x_lo, _sgd_arg(sgd))
 
 
-def conv_wgrad(dy, x, gw, stride: int, pad: int, dy_planes=None, x_planes=None, sgd=None) -> bool:
+def conv_wgrad_bn_bwd_ok(x_shape, Co: int, KH: int, KW: int, x_dtype=F32) -> bool:
+    """conv_wgrad(bn_bwd=) serves the weight gradient of a conv of a contiguous fp32 input
+    [K, B, H, W, C] with Co output channels: the fp32 TN kernel's BN-backward loader exists for the
+    tile the launch resolves to (csrc/conv_f32.hip) and the operands fit one launch."""
+    K, B, H, W, C = x_shape
+    if x_dtype != F32 or Co % 8 or C % 8:
+        return False
+    return bool(_C.conv_tn_f32_bn_bwd_ok(K, Co, KH * KW * C, Co, C, tn_f32_variant))
+
+
+def conv_wgrad(dy, x, gw, stride: int, pad: int, dy_planes=None, x_planes=None, sgd=None, bn_bwd=None) -> bool:
     """dW of a conv into the fp32 gradient rows gw [K, Co, KH, KW, Ci]. `dy_planes` /
     `x_planes` (fp32 only, both or neither): pre-split operands (split_planes), read by the
     LDS-DMA GEMM of csrc/conv_pl.hip when the shape allows (planes_ok). `sgd` (a FusedSGD ref,
-    plane path only): the kernel steps the weights instead of storing dW — returns True then."""
+    plane path only): the kernel steps the weights instead of storing dW — returns True then.
+    `bn_bwd` = (dy_out, x_bn, mask, coef [K, Co, 3], valid_rows) (fp32, no planes, a shape
+    conv_wgrad_bn_bwd_ok accepts): dY is the input gradient of a BatchNorm(+ReLU) that was never
+    written — `dy_out` the BN's output gradient and `x_bn` its input (both [K, M, Co] fp32
+    contiguous), `mask` the ReLU bits or None, `coef` bn_bwd(coef_out=)'s coefficients — and the
+    kernel's dY loader applies the BN backward (bn_bwd's own apply pass, bit for bit); `dy` only
+    gives the shape."""
     K, B, OH, OW, Co = dy.shape
     _, _, H, W, C = x.shape
+    if bn_bwd is not None:
+        dyo, xb, mk, cf, vr = bn_bwd
+        M = B * OH * OW
+        assert dy_planes is None and x_planes is None and sgd is None and dy.dtype == F32 and x.dtype == F32
+        assert max(M * Co, B * H * W * C) * 4 < WINDOW and x.is_contiguous()
+        assert conv_wgrad_bn_bwd_ok(x.shape, Co, gw.shape[2], gw.shape[3])
+        assert dyo.dtype == F32 and xb.dtype == F32 and dyo.is_contiguous() and xb.is_contiguous()
+        assert dyo.numel() == K * M * Co and xb.numel() == K * M * Co
+        assert cf.shape == (K, Co, 3) and cf.dtype == F32 and cf.is_contiguous(), cf.shape
+        if mk is not None:
+            assert mk.dtype == torch.uint8 and mk.is_contiguous() and mk.numel() == K * M * Co // 8
+        if vr is not None:
+            vr = vr.to(torch.int32).contiguous()
+            assert vr.shape == (K,)
+        assert gw.dtype == torch.float32 and gw.shape[0] == K and gw[0].is_contiguous()
+        _, Co2, KH, KW, Ci = gw.shape
+        assert Co2 == Co and Ci == C
+        R = KH * KW * C
+        splitk = _C.conv_tn_splitk(K, Co, R, M, C, tn_f32_variant, 1, Co, C, 0)
+        part = NULL
+        if splitk > 1:
+            if OPTIONS.deterministic:
+                part = _p(_tn_part(splitk * K * Co * R, gw.device))
+            else:
+                gw.zero_()
+        _C.conv_tn_bn_bwd(_p(dyo), _p(x), _p(gw), x.stride(0), gw.stride(0), B, H, W, C, OH, OW, KH, KW, stride, pad, M,
+                          Co, R, K, tn_f32_variant, _s(), C, part, _p(xb), _p(mk), _p(cf), _p(vr))
+        return False
     per_sample = max(OH * OW * Co, H * W * C) * dy.element_size()
     if B * per_sample >= WINDOW and dy_planes is None:
         # Σ over batch chunks of the chunk weight gradients (fp32, chunk order fixed)
@@ -715,7 +759,7 @@ def planes_buffer(shape, device):
 
 
 def bn_fwd(x, gamma, beta, valid_rows=None, relu=False, residual=None, eps=1e-5, with_mask=False, pre_stats=None,
-           planes: int = 0, res_coef=None):
+           planes: int = 0, res_coef=None, res_relu: bool = False):
     """Returns (y, mean, rstd); with_mask=True (ReLU, C % 8 == 0) also returns the 1-bit ReLU
     mask [K, R, C/8] uint8 that bn_bwd can read instead of y. `x` (and `residual`) may be
     channel slices of a wider buffer ([K, R, C] at row stride ld); y is contiguous.
@@ -726,7 +770,8 @@ def bn_fwd(x, gamma, beta, valid_rows=None, relu=False, residual=None, eps=1e-5,
     `res_coef` [K, C, 2] (fp32, with `residual`): the residual is the RAW input of a second
     BatchNorm without ReLU (same valid rows) whose (scale, shift) pairs bn_coef computed — its
     apply is folded into this one (y = act(bn(x) + scale·res + shift), the bits of applying it
-    first)."""
+    first). `res_relu` (with `res_coef`): that BatchNorm has a ReLU — the residual added is
+    max(scale·res + shift, 0), the fp32 values its own apply would have stored."""
     K, R, C = x.shape
     x, ldx = _pix_stride(x)
     assert x.stride(0) == R * ldx, "client stride of a strided BN input must be R*ld"
@@ -757,9 +802,11 @@ def bn_fwd(x, gamma, beta, valid_rows=None, relu=False, residual=None, eps=1e-5,
     assert gamma.dtype == x.dtype and (residual is None or residual.dtype == x.dtype)
     if res_coef is not None:
         assert residual is not None and x.dtype == F32 and res_coef.shape == (K, C, 2) and res_coef.is_contiguous()
+    assert res_coef is not None or not res_relu, "res_relu needs res_coef"
     _C.bn_fwd(_p(x), _p(gamma), _p(beta), _p(residual), _p(y), _p(mean), _p(rstd), _p(vr), g_cs, K, R, C, int(relu),
               eps, rep, _p(ws), _p(mask), _f32(x), _s(), ldx, _p(pre_stats),
-              0 if pre_stats is None else pre_stats.shape[1], _p(yp), int(planes != 2), NULL, 1, _p(res_coef))
+              0 if pre_stats is None else pre_stats.shape[1], _p(yp), int(planes != 2), NULL, 1, _p(res_coef),
+              int(bool(res_relu)))
     out = (y, mean, rstd, mask) if with_mask else (y, mean, rstd)
     return out + (yp,) if planes else out
 
@@ -1110,6 +1157,17 @@ def bn_bwd_apply_planes(dy, x, relu_mask, coef, valid_rows, dxp) -> None:
     vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
     _C.bn_bwd(_p(dy), _p(x), NULL, NULL, NULL, NULL, _p(vr), 0, K, R, C, int(relu_mask is not None), _p(dxp), NULL,
               NULL, NULL, 0, _p(ws), _p(relu_mask), 1, _s(), C, 0, _p(dxp), 0, NULL, 0, _p(coef), 2)
+
+
+def bn_bwd_apply_f32(dy, x, relu_mask, coef, valid_rows, dx) -> None:
+    """bn_bwd_apply_planes with the fp32 dX as the output: `dx` [K, R, C] fp32 contiguous."""
+    K, R, C = x.shape
+    assert dy.shape == x.shape and dy.is_contiguous() and x.is_contiguous() and dy.dtype == F32 == x.dtype
+    assert coef.shape == (K, C, 3) and dx.shape == (K, R, C) and dx.dtype == F32 and dx.is_contiguous()
+    ws = _workspace(_C.bn_workspace_floats(K, R, C), x.device)
+    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
+    _C.bn_bwd(_p(dy), _p(x), NULL, NULL, NULL, NULL, _p(vr), 0, K, R, C, int(relu_mask is not None), _p(dx), NULL,
+              NULL, NULL, 0, _p(ws), _p(relu_mask), 1, _s(), C, 0, NULL, 1, NULL, 0, _p(coef), 2)
 
 
 # ------------------------------------------------------------------------ layernorm
