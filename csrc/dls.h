@@ -579,6 +579,13 @@ void sgd_step(float* theta, const float* grad, float* mom, bf16_t* shadow, bf16_
               const uint8_t* active,
               const uint8_t* first, int K, long P, long ld, float wd, float momentum, float dampening, int nesterov,
               hipStream_t s);
+// sgd_step on g' = fl32(fl32(g + corr[k]) + fl32(mu · fl32(θ[k] − anchor))), each operation rounded
+// to fp32 once (the bits of forming g' with elementwise passes, then sgd_step); g' is not stored.
+// corr [K][corr_ld] fp32 or null (term skipped); anchor [P] fp32, read only when mu != 0.
+void sgd_step_corrected(float* theta, const float* grad, float* mom, bf16_t* shadow, bf16_t* split, const float* lr,
+                        const uint8_t* active, const uint8_t* first, int K, long P, long ld, float wd, float momentum,
+                        float dampening, int nesterov, const float* corr, long corr_ld, const float* anchor, float mu,
+                        hipStream_t s);
 // sgd_step over the float4 spans of a block table seg[b] = (first float4 of the row, count ≤ 2048):
 // the parameters whose gradients stepped themselves in their wgrad kernels are left out
 void sgd_step_seg(float* theta, const float* grad, float* mom, bf16_t* split, const float* lr, const uint8_t* active,

@@ -344,6 +344,89 @@ __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ theta, con
   }
 }
 
+// The flat step on the drift-corrected gradient g' = g + corr[k] + mu·(θ[k] − anchor) (FedProx: mu,
+// SCAFFOLD: corr = c − c_i), g' never stored. Each operation of g' is rounded to fp32 on its own
+// (nothing contracts into an FMA, see sgd_epi.h and the product below), so the result has the bits of forming
+// g' with separate elementwise passes and running sgd_kernel on it. Its own kernel, not a flag of
+// sgd_kernel: the plain step keeps its registers. corr / anchor may be null (then mu == 0 for
+// anchor); sgd_kernel<false>'s geometry and its loads-before-stores trips.
+__global__ void __launch_bounds__(256) sgd_corr_kernel(float* __restrict__ theta, const float* __restrict__ grad,
+                                                       float* __restrict__ mom, bf16_t* __restrict__ shadow,
+                                                       bf16_t* __restrict__ split, const float* __restrict__ lr,
+                                                       const uint8_t* __restrict__ active,
+                                                       const uint8_t* __restrict__ first, long P4, long ld, float wd,
+                                                       float momentum, float dampening, int nesterov,
+                                                       const float* __restrict__ corr, long corr_ld,
+                                                       const float* __restrict__ anchor, float mu) {
+  const int k = blockIdx.y;
+  if (!active[k]) return;
+  const float a = lr[k];
+  const bool fs = first[k] != 0;
+  const long base = (long)k * ld;
+  const long cbase = (long)k * corr_ld;
+  const bool prox = mu != 0.f;
+  SgdEpi e{};
+  e.wd = wd;
+  e.momentum = momentum;
+  e.dampening = dampening;
+  e.nesterov = nesterov;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < P4; i0 += 2 * stride) {
+    float4 t[2], g[2], m[2], c[2], w[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const long i = i0 + u * stride;
+      if (i < P4) {
+        t[u] = reinterpret_cast<float4*>(theta + base)[i];
+        g[u] = reinterpret_cast<const float4*>(grad + base)[i];
+        if (momentum != 0.f) m[u] = reinterpret_cast<float4*>(mom + base)[i];
+        if (corr) c[u] = reinterpret_cast<const float4*>(corr + cbase)[i];
+        if (prox) w[u] = reinterpret_cast<const float4*>(anchor)[i];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const long i = i0 + u * stride;
+      if (i >= P4) break;
+      float tv[4] = {t[u].x, t[u].y, t[u].z, t[u].w}, gv[4] = {g[u].x, g[u].y, g[u].z, g[u].w};
+      float mv[4] = {0.f, 0.f, 0.f, 0.f};
+      if (momentum != 0.f) {
+        mv[0] = m[u].x;
+        mv[1] = m[u].y;
+        mv[2] = m[u].z;
+        mv[3] = m[u].w;
+      }
+      if (corr) {
+        const float cv[4] = {c[u].x, c[u].y, c[u].z, c[u].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = __fadd_rn(gv[j], cv[j]);
+      }
+      if (prox) {
+        const float wv[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          // (__fmul_rn is a plain product to the compiler, and under -ffp-contract=fast the backend
+          // would fuse it into the add: the empty asm makes the rounded product opaque to it)
+          float pj = __fmul_rn(mu, __fsub_rn(tv[j], wv[j]));
+          asm volatile("" : "+v"(pj));
+          gv[j] = __fadd_rn(gv[j], pj);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tv[j] = sgd_epi_core(e, fs, a, tv[j], gv[j], mv[j]);
+      reinterpret_cast<float4*>(theta + base)[i] = make_float4(tv[0], tv[1], tv[2], tv[3]);
+      if (momentum != 0.f) reinterpret_cast<float4*>(mom + base)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
+      if (shadow) {
+        uint2 uu;
+        uu.x = (uint32_t)f2bf(tv[0]) | ((uint32_t)f2bf(tv[1]) << 16);
+        uu.y = (uint32_t)f2bf(tv[2]) | ((uint32_t)f2bf(tv[3]) << 16);
+        reinterpret_cast<uint2*>(shadow + base)[i] = uu;
+      }
+      if (split) store_split4(split, k, ld, i, tv);
+    }
+  }
+}
+
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ theta, const float* __restrict__ grad,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    bf16_t* __restrict__ shadow, const float* __restrict__ lr,
@@ -969,6 +1052,17 @@ void sgd_step(float* theta, const float* grad, float* mom, bf16_t* shadow, bf16_
   dim3 grid(grid_for(P4, 256, 1024), K);
   hipLaunchKernelGGL(sgd_kernel<false>, grid, dim3(256), 0, s, theta, grad, mom, shadow, split, lr, active, first, P4,
                      ld, wd, momentum, dampening, nesterov, (const long2*)nullptr);
+}
+
+void sgd_step_corrected(float* theta, const float* grad, float* mom, bf16_t* shadow, bf16_t* split, const float* lr,
+                        const uint8_t* active, const uint8_t* first, int K, long P, long ld, float wd, float momentum,
+                        float dampening, int nesterov, const float* corr, long corr_ld, const float* anchor, float mu,
+                        hipStream_t s) {
+  if (K == 0 || P == 0) return;
+  const long P4 = P / 4;
+  dim3 grid(grid_for(P4, 256, 1024), K);
+  hipLaunchKernelGGL(sgd_corr_kernel, grid, dim3(256), 0, s, theta, grad, mom, shadow, split, lr, active, first, P4, ld,
+                     wd, momentum, dampening, nesterov, corr, corr_ld, anchor, mu);
 }
 
 void sgd_step_seg(float* theta, const float* grad, float* mom, bf16_t* split, const float* lr, const uint8_t* active,

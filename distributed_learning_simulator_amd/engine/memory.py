@@ -49,9 +49,10 @@ def _gc_phase(phase: str, info: dict) -> None:
 gc.callbacks.append(_gc_phase)
 
 
-def state_bytes_per_client(layout, compute_dtype, optimizer: str) -> int:
+def state_bytes_per_client(layout, compute_dtype, optimizer: str, extra_rows: int = 0) -> int:
+    """`extra_rows`: further fp32 [P] rows a method keeps per resident client (SCAFFOLD's c − c_i)."""
     P = layout.padded_size
-    n = 3 * 4 * P  # theta, grad, state1
+    n = (3 + int(extra_rows)) * 4 * P  # theta, grad, state1
     if optimizer.lower() == "adam":
         n += 4 * P
     if compute_dtype != torch.float32:
@@ -115,17 +116,21 @@ def probe_activation_bytes(model, dc, hyper, device, compute_dtype) -> int:
 
 
 def plan_capacity(wanted: int, layout, model, dc, hyper, device, compute_dtype,
-                  fraction: float = 0.80, explicit: int = 0) -> int:
-    """Cohort size for this rank. `explicit` > 0 (config `cohort_size`) wins."""
+                  fraction: float = 0.80, explicit: int = 0, extra_rows: int = 0, reserved_bytes: int = 0) -> int:
+    """Cohort size for this rank. `explicit` > 0 (config `cohort_size`) wins. `extra_rows`: fp32
+    [P] rows the method adds per resident client; `reserved_bytes`: device memory the method will
+    allocate outside the cohort buffers (SCAFFOLD's per-client variate store), taken out of the
+    free memory before the budget fraction."""
     if explicit:
         return max(1, min(wanted, explicit))
     if device.type != "cuda" or wanted <= 1:
         return max(1, wanted)
-    state = state_bytes_per_client(layout, compute_dtype, hyper.optimizer_name)
+    state = state_bytes_per_client(layout, compute_dtype, hyper.optimizer_name, extra_rows=extra_rows)
     with DEVICE_LOCK:
         act = probe_activation_bytes(model, dc, hyper, device, compute_dtype)
     per_client = state + int(act * 1.15)  # allocator slack
     free, _total = torch.cuda.mem_get_info(device)
+    free = max(0, free - int(reserved_bytes))
     cap = max(1, min(wanted, int(math.floor(fraction * free / max(per_client, 1)))))
     get_logger().info("memory plan: %.1f MiB state + %.1f MiB activations per client, %.1f GiB free "
                       "-> %d of %d clients resident per wave", state / 2**20, act / 2**20, free / 2**30, cap, wanted)

@@ -158,6 +158,10 @@ class CohortBuffers:
             if (compute_dtype == torch.float32 and torch.device(device).type == "cuda"
                 and optimizer.lower() != "adam") else None
         )
+        # step correction (CohortTrainer.set_step_correction): θ_g of the round [P], and SCAFFOLD's
+        # c − c_i rows [capacity, P]; allocated once, captured step graphs hold their addresses
+        self.anchor: torch.Tensor | None = None
+        self.corr: torch.Tensor | None = None
 
     @property
     def compute(self) -> torch.Tensor:
@@ -165,7 +169,7 @@ class CohortBuffers:
 
     def nbytes(self) -> int:
         n = 0
-        for t in (self.theta, self.grad, self.state1, self.state2, self.shadow, self.split):
+        for t in (self.theta, self.grad, self.state1, self.state2, self.shadow, self.split, self.anchor, self.corr):
             if t is not None:
                 n += t.numel() * t.element_size()
         return n

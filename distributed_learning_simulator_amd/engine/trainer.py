@@ -150,6 +150,41 @@ class CohortTrainer:
         self.hooks = HookRegistry()
         self.adam_step_count = torch.zeros(capacity, dtype=torch.float32, device=self.device)
         self.graph = dataset_collection.graph
+        self._corr_mu: float | None = None  # step correction (set_step_correction); None: plain steps
+        self._corr_variates = False
+
+    # ------------------------------------------------------------ step correction
+    def set_step_correction(self, mu: float, variates: bool) -> None:
+        """Every local SGD step from now on runs on the drift-corrected gradient
+        g' = g + corr[k] + mu·(θ_k − θ_g) (`fl.sgd_step_corrected`): FedProx (mu > 0) and SCAFFOLD
+        (`variates`: corr[k] = c − c_i, filled per wave by `load_correction`). Called once, before
+        any training: the buffers (`buffers.anchor` [P], `buffers.corr` [capacity, P]) are static,
+        because captured step graphs hold their addresses. No step hook is involved, so sub-cohort
+        streams, ragged steps and graph replay stay on; the fused weight-gradient step is off
+        (`fused_sgd`), since its epilogues know nothing of g'."""
+        if self._graphs:
+            raise RuntimeError("set_step_correction after a step graph was created: the graphs step without it")
+        if self.hyper.optimizer_name.lower() == "adam":
+            raise ValueError("step correction (fed_prox / fed_scaffold) needs SGD: the Adam kernel gets no correction")
+        if self._corr_mu is not None:
+            raise RuntimeError("set_step_correction is called once")
+        b = self.buffers
+        P = b.theta.shape[1]
+        self._corr_mu = float(mu)
+        self._corr_variates = bool(variates)
+        b.anchor = torch.zeros(P, dtype=torch.float32, device=self.device)
+        if variates:
+            b.corr = torch.zeros((self.capacity, P), dtype=torch.float32, device=self.device)
+
+    @property
+    def step_correction(self) -> bool:
+        return self._corr_mu is not None
+
+    def load_correction(self, rows: torch.Tensor) -> None:
+        """buffers.corr[:K] = rows [K, P] (SCAFFOLD: c − c_i of the wave's clients)."""
+        if self.buffers.corr is None:
+            raise RuntimeError("load_correction needs set_step_correction(..., variates=True)")
+        self.buffers.corr[: rows.shape[0]].copy_(rows)
 
     # -------------------------------------------------------------- hook API (X4)
     def append_named_hook(self, point, name, fn):
@@ -163,6 +198,8 @@ class CohortTrainer:
         """Every resident client row k < K starts from θ_g (M1/M5 receive + load)."""
         shadow = self.buffers.shadow[:K] if self.buffers.shadow is not None else None
         fl.broadcast_rows(self.buffers.theta[:K], theta_g.to(self.device), shadow)
+        if self._corr_mu is not None:
+            self.buffers.anchor.copy_(theta_g)
         if self.hooks.has_hook(ExecutorHookPoint.AFTER_LOAD_MODEL):
             self.hooks.exec(ExecutorHookPoint.AFTER_LOAD_MODEL, theta=self.buffers.theta[:K])
 
@@ -291,9 +328,12 @@ class CohortTrainer:
 
     def fused_sgd(self, K: int, lr, active, first, row0: int = 0) -> FusedSGD | None:
         """This step's FusedSGD handle (the wgrad kernels step their weights), or None where the
-        flat step must see every gradient: Adam, bf16 compute (shadow rows), no live planes."""
+        flat step must see every gradient: Adam, bf16 compute (shadow rows), no live planes, a step
+        correction (the epilogues step on g, not g')."""
         b = self.buffers
         h = self.hyper
+        if self._corr_mu is not None:
+            return None
         if not (OPTIONS.fused_sgd and self._split_live and b.shadow is None and b.split is not None
                 and h.optimizer_name.lower() != "adam" and self.device.type == "cuda"):
             return None
@@ -332,6 +372,11 @@ class CohortTrainer:
             self.adam_step_count[r] += active.float()
             fl.adam_step(b.theta[r], b.grad[r], b.state1[r], b.state2[r], lr, active,
                          self.adam_step_count[r], weight_decay=h.weight_decay, shadow=shadow)
+        elif self._corr_mu is not None:
+            fl.sgd_step_corrected(b.theta[r], b.grad[r], b.state1[r], lr, active, first, h.weight_decay,
+                                  h.momentum, h.dampening, h.nesterov, self._corr_mu, b.anchor,
+                                  b.corr[r] if b.corr is not None else None, shadow,
+                                  b.split[r] if self._split_live else None)
         else:
             fl.sgd_step(b.theta[r], b.grad[r], b.state1[r], lr, active, first, h.weight_decay,
                         h.momentum, h.dampening, h.nesterov, shadow,

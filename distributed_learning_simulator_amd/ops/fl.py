@@ -3,6 +3,7 @@
 | primitive            | replaces (reference)                                           |
 |----------------------|----------------------------------------------------------------|
 | sgd_step             | torch.optim.SGD.step per client (K2), GradientWorker step (K3) |
+| sgd_step_corrected   | — (FedProx / SCAFFOLD local step: g + (c − c_i) + μ(θ − θ_g))    |
 | adam_step            | torch.optim.Adam.step per client                                |
 | broadcast_rows       | load_parameters of θ_g into every client (`util/model.py:6-23`)|
 | delta_rows           | ModelCache.get_parameter_diff (K4, `util/model_cache.py:30-36`)|
@@ -39,6 +40,26 @@ def sgd_step_seg(theta, grad, mom, lr, active, first_step, weight_decay, momentu
     """sgd_step over the spans of `seg_table` only (the rest stepped in their wgrad kernels)."""
     backend.get(theta).sgd_step_seg(theta, grad, mom, lr, active, weight_decay, momentum, dampening, nesterov,
                                     first_step, split, seg_table)
+
+
+def sgd_step_corrected(theta, grad, mom, lr, active, first_step, weight_decay, momentum, dampening, nesterov, mu,
+                       anchor, corr, shadow=None, split=None):
+    """The SGD step of `sgd_step` on the drift-corrected gradient of FedProx (mu > 0, corr None) and
+    SCAFFOLD (mu = 0, corr[k] = c − c_i); per active row k and element p
+
+      g1 = fl32(g + corr[k, p])                                   (corr None: g1 = g)
+      g2 = fl32(g1 + fl32(mu · fl32(θ[k, p] − anchor[p])))        (mu == 0: g2 = g1)
+      θ, m ← the `sgd_step` arithmetic on g2 (weight decay, momentum, nesterov after the correction)
+
+    every operation of the first two lines rounded to fp32 once, nothing contracted into an FMA.
+    Contract: θ, momentum, `shadow` and the `split` planes have the bits of materialising g' with
+    separate fp32 elementwise operations (`grad + corr`, `theta − anchor`, `· mu`, `+`) and calling
+    `sgd_step` on it; g' itself is never written, and `grad`, `corr` [K, P] fp32 (its own row stride
+    ≥ P) and `anchor` [P] fp32 (shared by all rows, required when mu != 0) are read-only. Inactive
+    rows, `first_step`, per-row `lr`, row strides ≥ P and P % 16 == 0 behave as in `sgd_step`.
+    Kernel: csrc/elementwise.hip sgd_corr_kernel; oracle and CPU path: ops/ref.py."""
+    backend.get(theta).sgd_step_corrected(theta, grad, mom, lr, active, weight_decay, momentum, dampening, nesterov,
+                                          first_step, mu, anchor, corr, shadow, split)
 
 
 def split_rows(theta, split):

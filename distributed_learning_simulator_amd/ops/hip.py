@@ -1577,6 +1577,33 @@ def sgd_step(theta, grad, mom, lr, active, weight_decay, momentum, dampening, ne
                 float(weight_decay), float(momentum), float(dampening), int(nesterov), _s())
 
 
+def sgd_step_corrected(theta, grad, mom, lr, active, weight_decay, momentum, dampening, nesterov, first_step, mu,
+                       anchor, corr, shadow=None, split=None):
+    """sgd_step on g' = g + corr[k] + mu·(θ[k] − anchor), formed in registers (csrc/elementwise.hip
+    sgd_corr_kernel; contract in ops.fl.sgd_step_corrected). `corr` [K, P] fp32 (own row stride) or
+    None; `anchor` [P] fp32, required when mu != 0."""
+    K, P, ld = _row_args(theta)
+    assert grad.stride(0) == ld and mom.stride(0) == ld
+    mu = float(mu)
+    corr_ld = 0
+    if corr is not None:
+        assert corr.dtype == torch.float32 and corr.shape == (K, P) and corr.stride(1) == 1 and corr.is_cuda
+        corr_ld = corr.stride(0)
+        assert corr_ld >= P and corr_ld % 4 == 0 and corr.data_ptr() % 16 == 0
+    if mu != 0.0:
+        assert anchor is not None, "mu != 0 needs the anchor row"
+        assert (anchor.dtype == torch.float32 and anchor.shape == (P,) and anchor.is_contiguous() and anchor.is_cuda
+                and anchor.data_ptr() % 16 == 0)
+    if shadow is not None:
+        assert shadow.stride(0) == ld and shadow.dtype == BF16
+    if split is not None:
+        assert split.shape == (K, 2, P) and split.is_contiguous() and split.dtype == BF16 and ld == P
+    _C.sgd_step_corrected(_p(theta), _p(grad), _p(mom), _p(shadow), _p(split), _p(lr.float().contiguous()),
+                          _p(active.to(torch.uint8).contiguous()), _p(first_step.to(torch.uint8).contiguous()), K, P,
+                          ld, float(weight_decay), float(momentum), float(dampening), int(nesterov), _p(corr), corr_ld,
+                          _p(anchor if mu != 0.0 else None), mu, _s())
+
+
 def sgd_step_seg(theta, grad, mom, lr, active, weight_decay, momentum, dampening, nesterov, first_step, split,
                  seg_table):
     """sgd_step over the spans of `seg_table` [n, 2] int64 (first float4 of the row, count): the

@@ -419,6 +419,21 @@ def sgd_step(theta, grad, mom, lr, active, weight_decay, momentum, dampening, ne
         split_rows(theta, split)
 
 
+def sgd_step_corrected(theta, grad, mom, lr, active, weight_decay, momentum, dampening, nesterov, first_step, mu,
+                       anchor, corr, shadow=None, split=None):
+    """The drift-corrected step, literally: g' from separate fp32 elementwise operations (each
+    rounded once), then `sgd_step` on it. `grad`, `corr` and `anchor` are not written."""
+    g = grad
+    if corr is not None:
+        g = g + corr
+    if mu != 0:
+        assert anchor is not None, "mu != 0 needs the anchor row"
+        d = theta - anchor.unsqueeze(0)
+        d = d * float(mu)
+        g = g + d
+    sgd_step(theta, g, mom, lr, active, weight_decay, momentum, dampening, nesterov, first_step, shadow, split)
+
+
 def adam_step(theta, grad, m, v, lr, active, step, beta1, beta2, eps, weight_decay, shadow=None):
     a = active.to(theta.device).bool()[:, None]
     g = grad + weight_decay * theta if weight_decay != 0 else grad

@@ -117,3 +117,4 @@ def dirichlet_split(labels: torch.Tensor, part_number: int, seed: int = 0, alpha
 
 # alias used by some configs / papers
 _REGISTRY["non_iid"] = random_label_iid_split
+_REGISTRY["dirichlet"] = dirichlet_split

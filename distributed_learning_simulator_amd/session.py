@@ -123,9 +123,15 @@ class Session:
             # `limited_resource` (reference aggregation_worker.py:124-130 spills the worker's model
             # cache to disk): here the rank gives client cohorts a quarter of the HBM budget it
             # otherwise would (more, smaller waves); client state never leaves the device
+            # a method's own device state (fed_scaffold: one correction row per resident client,
+            # and the per-client variate store outside the cohort buffers)
+            plan = getattr(CentralizedAlgorithmFactory.config[cfg.distributed_algorithm]["client_cls"],
+                           "memory_plan", None)
+            extra_rows, reserved = plan(cfg, self.layout) if plan is not None else (0, 0)
             capacity = plan_capacity(per_rank, self.layout, self.model, self.dc, self.hyper, self.device,
                                      self.compute_dtype, explicit=cfg.cohort_size,
-                                     fraction=0.2 if cfg.limited_resource else 0.8)
+                                     fraction=0.2 if cfg.limited_resource else 0.8, extra_rows=extra_rows,
+                                     reserved_bytes=reserved)
         self.trainer = CohortTrainer(self.model, self.dc, self.hyper, self.device, self.compute_dtype, capacity)
         self.trainer.debug = bool(cfg.debug)
         algo = cfg.distributed_algorithm

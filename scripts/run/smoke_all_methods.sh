@@ -33,5 +33,10 @@ $S --config-name fed_krum/mnist.yaml ++fed_krum.round=1 ++fed_krum.epoch=1 ++fed
    ++fed_krum.algorithm_kwargs.byzantine_number=1 ++fed_krum.debug=True
 $S --config-name fed_multi_krum/mnist.yaml ++fed_multi_krum.round=1 ++fed_multi_krum.epoch=1 ++fed_multi_krum.worker_number=5 \
    ++fed_multi_krum.algorithm_kwargs.byzantine_number=1 ++fed_multi_krum.algorithm_kwargs.byzantine_attack=nan ++fed_multi_krum.debug=True
+# client-drift corrections on non-IID shards: FedProx (proximal term) and SCAFFOLD (control variates);
+# two rounds, so that SCAFFOLD's second round steps on non-zero variates
+$S --config-name fed_prox/mnist.yaml ++fed_prox.round=2 ++fed_prox.epoch=1 ++fed_prox.worker_number=4 ++fed_prox.debug=True
+$S --config-name fed_scaffold/mnist.yaml ++fed_scaffold.round=2 ++fed_scaffold.epoch=1 ++fed_scaffold.worker_number=4 \
+   ++fed_scaffold.debug=True
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
