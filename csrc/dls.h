@@ -549,6 +549,24 @@ int pairwise_spans_per_wg(int n, long P);
 long pairwise_ws_doubles(int n, long P, int spw);
 void pairwise_sq_dists(const float* x, long ld, int n, long P, double* ws, int spw, double* out, hipStream_t s);
 
+// ---- client-level DP-FedAvg (csrc/dp.hip, ops/ref.py row_sq_norms / clip_scales / clipped_sum / gaussian_add)
+// out[k] (fp64 [n]) = Σ_p fl64(double(x[k][p])²) in the summation order of pairwise_sq_dists (spans of
+// PAIR_SPAN columns, groups of PAIR_GROUP spans). x [n][P]: row stride ld, rows 16-B aligned, P % 4 ==
+// 0. `ws`: row_sq_norms_ws_doubles(n, P) doubles of scratch, all written. Two launches, no atomics.
+long row_sq_norms_ws_doubles(int n, long P);
+void row_sq_norms(const float* x, long ld, int n, long P, double* ws, double* out, hipStream_t s);
+// scale[k] = clip / sqrt(nsq[k]) if sqrt(nsq[k]) > clip else 1.0 (sqrt and division correctly rounded);
+// a non-finite nsq[k]: scale[k] = 0, rejected[k] = 1 (else 0)
+void clip_scales(const double* nsq, double clip, int n, double* scale, uint8_t* rejected, hipStream_t s);
+// out[p] (fp64, p < P) = fl64(out[p] + fl64(scale[k]·double(x[k][p]))) for k ascending, rejected rows
+// skipped; scale / rejected [n] are scratch that clip_scales fills first in the same stream
+void clipped_sum(const float* x, long ld, int n, long P, const double* nsq, double clip, double* scale,
+                 uint8_t* rejected, double* out, hipStream_t s);
+// acc[p] (fp64, p < P) += fl64(std·z[p]) where mask[p] != 0 (mask null: everywhere); z = Box-Muller on
+// Philox4x32-10 with key (seed lo, seed hi) and counter (p/2 lo, p/2 hi, stream, 0x44503031)
+void gaussian_add(double* acc, const uint8_t* mask, long P, double std, unsigned long long seed, unsigned stream,
+                  hipStream_t s);
+
 // out[k][r][c] = keep(k, r, c) ? x·scale : 0 over [K][rows][N] (row stride ld), the dropout rule of
 // the GEMM epilogue; seeds [K]. f32: fp32 (else bf16) tensors.
 void dropout_apply(const void* x, void* out, int K, long rows, int N, long ld, const uint32_t* seeds, float p,

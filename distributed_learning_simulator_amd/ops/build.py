@@ -38,7 +38,10 @@ COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-mcode-
 FILE_FLAGS = {"compress.hip": ["-ffp-contract=on"],
               # krum.hip: d·d and the add that follows are rounded separately (the contract of
               # ops/ref.py pairwise_sq_dists): no contraction at all
-              "krum.hip": ["-ffp-contract=off"]}
+              "krum.hip": ["-ffp-contract=off"],
+              # dp.hip: x·x, s·x, std·z and the adds that follow are rounded separately (the contracts
+              # of ops/ref.py row_sq_norms / clipped_sum / gaussian_add), and 2π·u2 is one product
+              "dp.hip": ["-ffp-contract=off"]}
 
 
 def _headers() -> list[str]:

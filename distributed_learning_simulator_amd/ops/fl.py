@@ -10,6 +10,9 @@
 | weighted_sum         | FedAVGAlgorithm accumulate (K6, `fed_avg_algorithm.py:39-52`)  |
 | trimmed_sum          | — (robust aggregation: trimmed mean / median, Yin et al. 2018)  |
 | pairwise_sq_dists    | — (Krum / Multi-Krum distances, Blanchard et al. 2017)           |
+| row_sq_norms         | — (DP-FedAvg per-client L2 norms, McMahan et al. 2018)           |
+| clipped_sum          | — (DP-FedAvg clipped fp64 accumulation)                          |
+| gaussian_add         | — (DP-FedAvg Gaussian mechanism, Philox4x32-10 + Box-Muller)     |
 | mix_rows             | Shapley subset models (K8, `aggregation_algorithm.py:30-50`)   |
 | masked_weighted_sum  | FedDropoutAvg aggregation (K10, `fed_dropout_avg/algorithm.py`)|
 | dropout_mask         | FedDropoutAvg Bernoulli mask (K9, `fed_dropout_avg/worker.py`) |
@@ -141,6 +144,73 @@ def krum_select(D, f: int, m: int, ids) -> list:
 def krum_scores(D, f: int):
     """(fp64 [n] Krum scores on the host, the f actually used): see `krum_select`."""
     return ref.krum_scores(D, f)
+
+
+def row_sq_norms(x, out=None):
+    """fp64 [n] squared L2 norms of the rows of x [n, P] fp32 (row stride ≥ P, 16-B aligned rows), the
+    first pass of DP-FedAvg clipping (csrc/dp.hip; oracle and CPU path ops/ref.py).
+
+    term(k, p) = fl64(double(x[k, p]) · double(x[k, p])): the product is exact, a 24-bit mantissa
+    squared fits in 53 bits. The terms are added in the order `pairwise_sq_dists` defines: the columns
+    are cut into spans of W = ref.PAIR_SPAN = 4096 columns (the last may be shorter) and the spans into
+    groups of G = ref.PAIR_GROUP = 8 consecutive spans;
+      span sum  = the span's terms added one at a time in ascending column order from +0.0,
+      group sum = the group's span sums added in ascending span order from +0.0,
+      out[k]    = the group sums added in ascending group order from +0.0.
+    Denormal inputs are not flushed. Nothing depends on n, the launch geometry, the device or the rank:
+    out[k] has the bits of pairwise_sq_dists(stack([x[k], zeros]))[0, 1], zero columns change nothing,
+    a finite row whose sum does not overflow gives a finite norm, NaN / ±inf follow IEEE (NaN payload
+    bits are not part of the contract). No float atomics: bitwise reproducible, and the kernel and the
+    oracle agree bit for bit. Written into out[:n] if given."""
+    return backend.get(x).row_sq_norms(x, out)
+
+
+def clip_scales(nsq, clip):
+    """(s fp64 [n], rejected bool [n]): the per-row factors of L2 clipping to `clip` > 0 from the squared
+    norms nsq fp64 [n] (`row_sq_norms`).
+
+      norm = sqrt(nsq);  s = clip / norm if norm > clip, else exactly 1.0;
+      a non-finite nsq gives s = 0 and rejected = True — NaN or ±inf in the row, or a finite row
+      whose square sum overflows.
+    sqrt, the comparison and the division are correctly rounded IEEE operations, so both backends give
+    the same bits, and s · norm ≤ clip · (1 + 2^-52). `clipped_sum` forms the same factors on the
+    device; this function makes the rule observable."""
+    return backend.get(nsq).clip_scales(nsq, clip)
+
+
+def clipped_sum(x, nsq, clip, out=None):
+    """out (fp64 [≥ P]; zeros [P] if None)[:P] += Σ_k s_k · x[k, :] over the rows of x [n, P] fp32, with
+    (s, rejected) = clip_scales(nsq, clip): for rows in ascending k,
+
+      out[p] = fl64(out[p] + fl64(s_k · double(x[k, p])))
+
+    multiply and add rounded separately (no FMA; csrc/dp.hip is compiled with contraction off).
+    Rejected rows are skipped, not multiplied: 0 · NaN would poison the sum. An unclipped row (s_k =
+    1.0) adds double(x) exactly. s_k is formed on the device from `nsq` and `clip`: no host read
+    between `row_sq_norms` and this call. `out` accumulates in place across calls (waves, cohorts);
+    out[P:] is untouched; x and nsq are read-only. The kernel and the oracle agree bit for bit.
+    Returns `out`."""
+    return backend.get(x).clipped_sum(x, nsq, clip, out)
+
+
+def gaussian_add(acc, std: float, seed: int, stream: int, mask=None):
+    """acc (fp64 [P]) [p] += fl64(std · z[p]) for every p with mask[p] != 0 (`mask`: uint8 / bool [P], e.g.
+    the layout's valid_mask; None: every p). Masked-out elements are not written; std == 0 writes
+    nothing at all. seed: 64-bit int, stream: 32-bit int (the round number).
+
+    z is Box-Muller on Philox4x32-10 (Random123: multipliers 0xD2511F53, 0xCD9E8D57, Weyl increments
+    0x9E3779B9, 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32) and, for the pair index i = p // 2,
+    counter (i & 0xffffffff, i >> 32, stream, 0x44503031); the output words w0..w3 give
+      u1 = (((w0 >> 5) << 26) + (w1 >> 6) + 1) · 2^-53 in (0, 1],
+      u2 = (((w2 >> 5) << 26) + (w3 >> 6)) · 2^-53 in [0, 1),
+      r = sqrt(−2 · log(u1)), φ = fl64(2π · u2), z[2i] = r · cos φ, z[2i + 1] = r · sin φ, all in fp64.
+    z depends on (seed, stream, p) only: the same on every rank, in every launch geometry, across
+    waves. The integer stage is exact on both backends; log, cos and sin come from two different
+    libms, a few ulp apart, and r ≤ sqrt(2 · 53 · ln 2) = 8.57, so |z_kernel − z_oracle| ≲ 1.2e-14 (the
+    tests bound it by 1e-13). Returns `acc`."""
+    if float(std) == 0.0:
+        return acc
+    return backend.get(acc).gaussian_add(acc, float(std), int(seed), int(stream), mask)
 
 
 def mix_rows(x, w, out_dtype):

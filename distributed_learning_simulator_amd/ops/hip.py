@@ -1722,6 +1722,92 @@ def pairwise_sq_dists(x, out=None, scratch=None, spans_per_wg: int | None = None
     return out
 
 
+_dp_cache: dict = {}  # scratch of row_sq_norms / clipped_sum per (device, stream); grown, never shrunk
+
+
+def _dp_scratch(kind: str, need: int, dtype, device) -> torch.Tensor:
+    key = (kind, device, torch.cuda.current_stream().cuda_stream)
+    buf = _dp_cache.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _dp_cache[key] = torch.empty(max(need, 1), dtype=dtype, device=device)
+    return buf
+
+
+def row_sq_norms_scratch_doubles(n: int, P: int) -> int:
+    """Doubles of scratch a row_sq_norms launch of this shape writes (all of them)."""
+    return int(_C.row_sq_norms_ws_doubles(n, P))
+
+
+def row_sq_norms(x, out=None, scratch=None):
+    """csrc/dp.hip: fp64 [n] squared L2 norms of the rows of x [n, P] in the summation order of
+    `ops.ref.row_sq_norms`. `scratch` (fp64, ≥ row_sq_norms_scratch_doubles) replaces the cached
+    span-sum buffer. Written into out[:n] if given; out[n:] is not touched."""
+    n, P, ld = _row_args(x)
+    _check(x, F32, contiguous=False, name="x")
+    assert ld % 4 == 0 and x.data_ptr() % 16 == 0, "x: rows must be 16-B aligned"
+    need = int(_C.row_sq_norms_ws_doubles(n, P))
+    assert n * ((need // max(n, 1) + 63) // 64) < 2 ** 31, "too many rows"
+    if scratch is None:
+        scratch = _dp_scratch("spans", need, torch.float64, x.device)
+    _check(scratch, torch.float64, name="scratch")
+    assert scratch.numel() >= need
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=x.device)
+    _check(out, torch.float64, name="out")
+    assert out.dim() == 1 and out.numel() >= n
+    if n:
+        _C.row_sq_norms(_p(x), ld, n, P, _p(scratch), _p(out), _s())
+    return out
+
+
+def clip_scales(nsq, clip):
+    """csrc/dp.hip clip_scales_kernel: (s fp64 [n], rejected bool [n]) by the rule of `ops.ref.clip_scales`."""
+    clip = ref.check_clip(clip)
+    _check(nsq, torch.float64, name="nsq")
+    assert nsq.dim() == 1
+    n = nsq.numel()
+    s = torch.empty(n, dtype=torch.float64, device=nsq.device)
+    rej = torch.empty(n, dtype=torch.uint8, device=nsq.device)
+    if n:
+        _C.clip_scales(_p(nsq), clip, n, _p(s), _p(rej), _s())
+    return s, rej.bool()
+
+
+def clipped_sum(x, nsq, clip, out=None):
+    """csrc/dp.hip: out (fp64 [≥ P], zeros [P] if None)[:P] += Σ_k s_k · x[k, :], rows in ascending k, s
+    formed on the device from nsq and clip (no host read), rejected rows skipped; out[P:] untouched."""
+    n, P, ld = _row_args(x)
+    clip = ref.check_clip(clip)
+    _check(x, F32, contiguous=False, name="x")
+    assert ld % 4 == 0 and x.data_ptr() % 16 == 0, "x: rows must be 16-B aligned"
+    _check(nsq, torch.float64, name="nsq")
+    assert nsq.shape == (n,)
+    if out is None:
+        out = torch.zeros(P, dtype=torch.float64, device=x.device)
+    _check(out, torch.float64, name="out")
+    assert out.dim() == 1 and out.numel() >= P and out.data_ptr() % 32 == 0, "out: 32-B aligned fp64 [>= P]"
+    if n:
+        s = _dp_scratch("scale", n, torch.float64, x.device)
+        rej = _dp_scratch("rejected", n, torch.uint8, x.device)
+        _C.clipped_sum(_p(x), ld, n, P, _p(nsq), clip, _p(s), _p(rej), _p(out), _s())
+    return out
+
+
+def gaussian_add(acc, std, seed, stream, mask=None):
+    """csrc/dp.hip: acc (fp64 [P]) [p] += std · z[p] where mask[p] != 0; z as `ops.ref.gaussian_noise`."""
+    _check(acc, torch.float64, name="acc")
+    assert acc.dim() == 1
+    P = acc.numel()
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        _check(mask, torch.uint8, name="mask")
+        assert mask.shape == (P,)
+    if P:
+        _C.gaussian_add(_p(acc), _p(mask), P, float(std), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, _s())
+    return acc
+
+
 def mix_rows(x, w, out_dtype=BF16):
     """[M, P] = W[M, K] · x[K, P]: subset models for Shapley utilities, emitted in the eval
     compute dtype (bf16 or fp32) by one native pass that reads each x row once per 32 models;

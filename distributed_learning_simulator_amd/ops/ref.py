@@ -15,6 +15,8 @@ of implicit compute sites these replace is SURVEY §2.5 (K1-K23).
 
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -560,6 +562,156 @@ def pairwise_sq_dists(x, out=None):
     assert out.dtype == torch.float64 and out.shape == (n, n)
     out.copy_(res)
     return out
+
+
+def row_sq_norms(x, out=None):
+    """Squared L2 norm of every row of x [n, P] fp32 (the oracle of csrc/dp.hip row_sq_norms, and the
+    CPU path): fp64 [n] (written into out[:n] if given).
+
+    term(k, p) = fl64(double(x[k, p]) · double(x[k, p])) — exact, a 24-bit mantissa squared fits in 53
+    bits — added in the order of `pairwise_sq_dists`: spans of W = PAIR_SPAN columns one term at a time
+    in ascending column order from +0.0, groups of G = PAIR_GROUP span sums in ascending span order
+    from +0.0, the group sums in ascending group order from +0.0. Denormals are not flushed; nothing
+    depends on n. So row_sq_norms(x)[k] has the bits of pairwise_sq_dists(stack([x[k], zeros]))[0, 1].
+
+    Like `pairwise_sq_dists`, the loops run over the position inside a span (all spans at once), the
+    span inside a group, then the groups: plain tensor adds, no `sum` / `cumsum`."""
+    n, P = x.shape
+    assert x.dtype == torch.float32
+    W, G = PAIR_SPAN, PAIR_GROUP
+    xd = x.double()
+    full, tail = P // W, P % W
+    sums = torch.zeros((full + (1 if tail else 0), n), dtype=torch.float64, device=x.device)  # per span
+    if full:
+        cols = xd[:, : full * W].reshape(n, full, W).permute(2, 1, 0).contiguous()  # [W, span, row]
+        acc = sums[:full]
+        for c in range(W):
+            acc.add_(cols[c] * cols[c])
+    if tail:
+        cols = xd[:, full * W :].t().contiguous()  # [tail, row]
+        acc = sums[full]
+        for c in range(tail):
+            acc.add_(cols[c] * cols[c])
+    res = torch.zeros(n, dtype=torch.float64, device=x.device)
+    for g0 in range(0, sums.shape[0], G):
+        group = torch.zeros(n, dtype=torch.float64, device=x.device)
+        for s in range(g0, min(g0 + G, sums.shape[0])):
+            group = group + sums[s]
+        res = res + group
+    if out is None:
+        return res
+    assert out.dtype == torch.float64 and out.dim() == 1 and out.numel() >= n
+    out[:n].copy_(res)
+    return out
+
+
+def check_clip(clip) -> float:
+    clip = float(clip)
+    if not (clip > 0.0 and math.isfinite(clip)):
+        raise ValueError(f"the clip norm must be a finite positive number, got {clip}")
+    return clip
+
+
+def clip_scales(nsq, clip):
+    """(s fp64 [n], rejected bool [n]) of squared norms nsq fp64 [n]: norm = sqrt(nsq); s = clip / norm
+    if norm > clip, else exactly 1.0; a non-finite nsq (NaN or ±inf in the row, or a finite row whose
+    square sum overflows) gives s = 0 and rejected = True. sqrt, the comparison and the division are
+    correctly rounded IEEE operations: the same bits on every backend. (Evaluated with python floats
+    over the n values: `torch.sqrt` on the CPU is not correctly rounded in every build.)"""
+    clip = check_clip(clip)
+    assert nsq.dtype == torch.float64 and nsq.dim() == 1
+    s, rejected = [], []
+    for v in nsq.tolist():
+        bad = not math.isfinite(v)
+        norm = math.sqrt(v) if not bad and v >= 0.0 else float("nan")
+        s.append(0.0 if bad else clip / norm if norm > clip else 1.0)
+        rejected.append(bad)
+    return (torch.tensor(s, dtype=torch.float64, device=nsq.device),
+            torch.tensor(rejected, dtype=torch.bool, device=nsq.device))
+
+
+def clipped_sum(x, nsq, clip, out=None):
+    """out (fp64 [≥ P]; zeros [P] if None)[:P] += the rows of x [n, P] fp32 scaled by `clip_scales(nsq,
+    clip)`: for k ascending, out[p] = fl64(out[p] + fl64(s_k · double(x[k, p]))), multiply and add
+    rounded separately; rejected rows are skipped (0 · NaN would poison the sum). An unclipped row
+    (s_k = 1.0) adds double(x) exactly. The oracle of csrc/dp.hip clipped_sum, and the CPU path."""
+    n, P = x.shape
+    assert x.dtype == torch.float32 and nsq.shape == (n,)
+    s, rejected = clip_scales(nsq, clip)
+    if out is None:
+        out = torch.zeros(P, dtype=torch.float64, device=x.device)
+    assert out.dtype == torch.float64 and out.dim() == 1 and out.numel() >= P
+    acc = out[:P]
+    s_host, rej_host = s.tolist(), rejected.tolist()
+    for k in range(n):
+        if rej_host[k]:
+            continue
+        acc.add_(x[k].double() * s_host[k])
+    return out
+
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57  # Random123 Philox4x32 multipliers
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85  # ... and Weyl key increments
+DP_NOISE_TAG = 0x44503031  # fourth counter word of gaussian_add ("DP01")
+_M32 = 0xFFFFFFFF
+
+
+def _mulhilo32(m: int, a):
+    """(high, low) 32-bit words of m · a for a 32-bit constant m and int64 tensors a < 2^32. The
+    product exceeds 2^63, so it is formed from 16-bit halves (every partial sum stays below 2^34)."""
+    mh, ml = m >> 16, m & 0xFFFF
+    ah, al = a >> 16, a & 0xFFFF
+    mid = ah * ml + al * mh
+    low = al * ml + ((mid & 0xFFFF) << 16)
+    return ah * mh + (mid >> 16) + (low >> 32), low & _M32
+
+
+def philox4x32(counter, key, rounds: int = 10):
+    """Philox4x32-`rounds` (Salmon et al. 2011; the Random123 constants). counter: four int64 tensors
+    (or ints) holding 32-bit words, key: two ints. Returns the four output words as int64 tensors."""
+    c0, c1, c2, c3 = (torch.as_tensor(c, dtype=torch.int64) & _M32 for c in counter)
+    k0, k1 = int(key[0]) & _M32, int(key[1]) & _M32
+    for _ in range(rounds):
+        hi0, lo0 = _mulhilo32(PHILOX_M0, c0)
+        hi1, lo1 = _mulhilo32(PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + PHILOX_W0) & _M32, (k1 + PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def gaussian_noise(P: int, seed: int, stream: int, start: int = 0, device=None):
+    """fp64 [P] standard normal draws z[start], ..., z[start + P − 1] of the (seed, stream) sequence:
+    for the pair index i = p // 2, Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+    (i & 0xffffffff, i >> 32, stream, 0x44503031) gives w0..w3,
+      u1 = (((w0 >> 5) << 26) + (w1 >> 6) + 1) · 2^-53 in (0, 1],
+      u2 = (((w2 >> 5) << 26) + (w3 >> 6)) · 2^-53 in [0, 1),
+      r = sqrt(−2 · log(u1)), φ = fl64(2π · u2), z[2i] = r · cos φ, z[2i + 1] = r · sin φ  (Box-Muller),
+    all in fp64. z[p] depends on (seed, stream, p) only."""
+    seed, stream = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & _M32
+    first, last = start // 2, (start + P + 1) // 2
+    i = torch.arange(first, max(last, first), dtype=torch.int64, device=device)
+    w0, w1, w2, w3 = philox4x32((i & _M32, i >> 32, torch.full_like(i, stream), torch.full_like(i, DP_NOISE_TAG)),
+                                (seed & _M32, seed >> 32))
+    u1 = (((w0 >> 5) << 26) + (w1 >> 6) + 1).double() * 2.0 ** -53
+    u2 = (((w2 >> 5) << 26) + (w3 >> 6)).double() * 2.0 ** -53
+    r = torch.sqrt(-2.0 * torch.log(u1))
+    phi = (2.0 * math.pi) * u2
+    z = torch.stack([r * torch.cos(phi), r * torch.sin(phi)], dim=1).reshape(-1)
+    return z[start - 2 * first : start - 2 * first + P]
+
+
+def gaussian_add(acc, std, seed, stream, mask=None):
+    """acc (fp64 [P]) [p] += fl64(std · z[p]) wherever mask[p] != 0 (`mask` None: everywhere), z =
+    `gaussian_noise(P, seed, stream)`. Masked-out elements are not written. Returns `acc`."""
+    assert acc.dtype == torch.float64 and acc.dim() == 1
+    P = acc.numel()
+    t = gaussian_noise(P, seed, stream, device=acc.device) * float(std)
+    if mask is None:
+        return acc.add_(t)
+    assert mask.shape == (P,)
+    m = mask != 0
+    acc[m] = acc[m] + t[m]
+    return acc
 
 
 def krum_scores(D, f: int):

@@ -329,6 +329,8 @@ class Session:
         if self.config.debug:
             self._debug_check(r, server.global_parameter)
         extra = {"failed_clients": len(failed)} if failed else {}
+        # a method's own per-round figures (fed_dp_avg: clipping statistics and the privacy spent)
+        extra.update(getattr(server.algorithm, "round_stats", None) or {})
         self.record_round(r, t0, active, up, down, marks=marks, **extra)
         return theta_recv
 

@@ -38,5 +38,7 @@ $S --config-name fed_multi_krum/mnist.yaml ++fed_multi_krum.round=1 ++fed_multi_
 $S --config-name fed_prox/mnist.yaml ++fed_prox.round=2 ++fed_prox.epoch=1 ++fed_prox.worker_number=4 ++fed_prox.debug=True
 $S --config-name fed_scaffold/mnist.yaml ++fed_scaffold.round=2 ++fed_scaffold.epoch=1 ++fed_scaffold.worker_number=4 \
    ++fed_scaffold.debug=True
+$S --config-name fed_dp_avg/mnist.yaml ++fed_dp_avg.round=2 ++fed_dp_avg.epoch=1 ++fed_dp_avg.worker_number=4 \
+   ++fed_dp_avg.algorithm_kwargs.dp_clip_norm=0.05 ++fed_dp_avg.debug=True
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
