@@ -567,6 +567,20 @@ void clipped_sum(const float* x, long ld, int n, long P, const double* nsq, doub
 void gaussian_add(double* acc, const uint8_t* mask, long P, double std, unsigned long long seed, unsigned stream,
                   hipStream_t s);
 
+// ---- server optimisers (csrc/server_opt.hip, ops/ref.py server_opt_step)
+// One step of FedAvgM / FedAdagrad / FedAdam / FedYogi on d = target − θ, all fp64, every operation rounded
+// once: θ (fp32 [P], 16-B aligned, P % 4 == 0) in place, m / v (fp64 [P], 32-B aligned; v null for SGDM)
+// in place, target (fp64 [≥ P], 32-B aligned) read-only, x (fp64 [P] or null) the pre-cast result. The rule
+// indices are the positions in ops/ref.py SERVER_OPT_RULES. Returns 0, or −1 (nothing launched) for a bad
+// rule, P or null operand. server_opt_max_blocks(): the grid cap of the grid-stride loop.
+#define SERVER_OPT_SGDM 0
+#define SERVER_OPT_ADAGRAD 1
+#define SERVER_OPT_ADAM 2
+#define SERVER_OPT_YOGI 3
+int server_opt_max_blocks();
+int server_opt_step(float* theta, const double* target, double* m, double* v, double* x, long P, int rule, double lr,
+                    double beta1, double c1, double beta2, double c2, double tau, hipStream_t s);
+
 // out[k][r][c] = keep(k, r, c) ? x·scale : 0 over [K][rows][N] (row stride ld), the dropout rule of
 // the GEMM epilogue; seeds [K]. f32: fp32 (else bf16) tensors.
 void dropout_apply(const void* x, void* out, int K, long rows, int N, long ld, const uint32_t* seeds, float p,

@@ -1,0 +1,20 @@
+"""FedAdagrad (Reddi et al. 2021, "Adaptive federated optimization"): FedAvg whose server runs Adagrad on
+the rounds' pseudo-gradients, v' = v + d², θ' = θ + lr·m' / (sqrt(v') + τ)
+(`ops.fl.server_opt_step`, csrc/server_opt.hip; the stage is server/server_optimizer.py, which presets the
+rule `adagrad` from this method's name). Workers, uploads, aggregation and byte counts are FedAvg's;
+`algorithm_kwargs`: `server_lr`, `server_beta1`, `server_beta2`, `server_tau`. Not in the reference."""
+
+from ...algorithm.fed_avg_algorithm import FedAVGAlgorithm
+from ...server.aggregation_server import AggregationServer
+from ...topology.endpoints import ClientEndpoint, ServerEndpoint
+from ...worker.aggregation_worker import AggregationWorker
+from ..algorithm_factory import CentralizedAlgorithmFactory
+
+CentralizedAlgorithmFactory.register_algorithm(
+    algorithm_name="fed_adagrad",
+    client_cls=AggregationWorker,
+    server_cls=AggregationServer,
+    client_endpoint_cls=ClientEndpoint,
+    server_endpoint_cls=ServerEndpoint,
+    algorithm_cls=FedAVGAlgorithm,
+)

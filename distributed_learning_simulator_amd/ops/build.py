@@ -41,7 +41,10 @@ FILE_FLAGS = {"compress.hip": ["-ffp-contract=on"],
               "krum.hip": ["-ffp-contract=off"],
               # dp.hip: x·x, s·x, std·z and the adds that follow are rounded separately (the contracts
               # of ops/ref.py row_sq_norms / clipped_sum / gaussian_add), and 2π·u2 is one product
-              "dp.hip": ["-ffp-contract=off"]}
+              "dp.hip": ["-ffp-contract=off"],
+              # server_opt.hip: β·m, c·d, c·q, lr·m' and the sums that follow them are rounded separately
+              # (the contract of ops/ref.py server_opt_step, where each is its own statement)
+              "server_opt.hip": ["-ffp-contract=off"]}
 
 
 def _headers() -> list[str]:

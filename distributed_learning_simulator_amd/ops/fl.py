@@ -13,6 +13,7 @@
 | row_sq_norms         | — (DP-FedAvg per-client L2 norms, McMahan et al. 2018)           |
 | clipped_sum          | — (DP-FedAvg clipped fp64 accumulation)                          |
 | gaussian_add         | — (DP-FedAvg Gaussian mechanism, Philox4x32-10 + Box-Muller)     |
+| server_opt_step      | — (FedAvgM / FedAdagrad / FedAdam / FedYogi server step, Reddi 2021)|
 | mix_rows             | Shapley subset models (K8, `aggregation_algorithm.py:30-50`)   |
 | masked_weighted_sum  | FedDropoutAvg aggregation (K10, `fed_dropout_avg/algorithm.py`)|
 | dropout_mask         | FedDropoutAvg Bernoulli mask (K9, `fed_dropout_avg/worker.py`) |
@@ -211,6 +212,41 @@ def gaussian_add(acc, std: float, seed: int, stream: int, mask=None):
     if float(std) == 0.0:
         return acc
     return backend.get(acc).gaussian_add(acc, float(std), int(seed), int(stream), mask)
+
+
+def server_opt_step(theta, target, m, v, rule, lr, beta1=0.9, beta2=0.99, tau=1e-3, x_out=None):
+    """One step of a server optimiser on the pseudo-gradient d = target − θ (FedAvgM, Hsu et al. 2019;
+    FedAdagrad / FedAdam / FedYogi, Reddi et al. 2021, no bias correction). theta fp32 [P] is θ_t and
+    becomes θ_{t+1} in place; target fp64 [≥ P] is what the aggregation produced (read-only, target[P:]
+    is not read); m, v fp64 [P] are the state, updated in place (v is None for `sgdm`); x_out (fp64 [P],
+    optional) receives the pre-cast x. rule ∈ `ref.SERVER_OPT_RULES`. c1 = 1.0 − beta1 and c2 = 1.0 −
+    beta2 are formed here, once, in python doubles, and passed to both backends. Per element p:
+
+      d  = target[p] − double(θ[p])
+      q  = d·d
+      m' = β1·m + d                      (sgdm)
+      m' = β1·m + c1·d                   (adagrad, adam, yogi)
+      v' = v + q                         (adagrad)
+      v' = β2·v + c2·q                   (adam)
+      v' = v − (c2·q)·sign(v − q)        (yogi; sign is −1, 0 or +1 and 0 for 0 and NaN: the product is exact)
+      x  = double(θ) + lr·m'             (sgdm)
+      x  = double(θ) + (lr·m') / (sqrt(v') + τ)    (adagrad, adam, yogi)
+      θ'[p] = fl32(x)                    (round to nearest even, overflow to ±inf)
+
+    Every operation is an fp64 operation rounded once; nothing is contracted into an FMA
+    (csrc/server_opt.hip is compiled with contraction off); sqrt and / are the correctly rounded IEEE
+    operations; denormals are not flushed. A non-finite d (NaN or ±inf in target[p] or θ[p]) gives θ'[p]
+    = fl32(target[p]) and x = target[p], and m[p], v[p] keep their bits: the poisoned coordinate shows
+    in θ as it does under plain aggregation, the state is not poisoned for good. Layout padding (θ =
+    +0, target = +0) keeps +0 bits. Nothing outside [0, P) of any buffer is written. P % 4 == 0, theta
+    16-B aligned, the fp64 buffers 32-B aligned; an unknown rule, a non-finite lr / β / τ, β outside [0,
+    1), τ ≤ 0 for an adaptive rule or a misplaced operand raises ValueError before any launch. No
+    atomics, one writer per element: two launches give the same bits, and the kernel and the oracle
+    (`ops.ref.server_opt_step`, also the CPU path) agree bit for bit on θ', m', v' and x (NaN payload
+    bits are not part of the contract). Returns `theta`."""
+    rule, lr, beta1, beta2, tau = ref.check_server_opt(rule, lr, beta1, beta2, tau)
+    c1, c2 = 1.0 - beta1, 1.0 - beta2
+    return backend.get(theta).server_opt_step(theta, target, m, v, rule, lr, beta1, beta2, tau, c1, c2, x_out)
 
 
 def mix_rows(x, w, out_dtype):

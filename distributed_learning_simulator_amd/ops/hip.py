@@ -1808,6 +1808,26 @@ def gaussian_add(acc, std, seed, stream, mask=None):
     return acc
 
 
+def server_opt_max_elements() -> int:
+    """Elements one trip of the server_opt_step grid-stride loop covers (grid cap · 256 lanes · 4)."""
+    return int(_C.server_opt_max_blocks()) * 256 * 4
+
+
+def server_opt_step(theta, target, m, v, rule, lr, beta1, beta2, tau, c1, c2, x_out=None):
+    """csrc/server_opt.hip: one server optimiser step by the arithmetic of `ops.ref.server_opt_step`; θ, m,
+    v in place, x to `x_out` if given. Operand errors raise ValueError before the launch."""
+    rule, lr, beta1, beta2, tau = ref.check_server_opt(rule, lr, beta1, beta2, tau)
+    P = ref.check_server_opt_operands(theta, target, m, v, rule, x_out)
+    if not theta.is_cuda:
+        raise ValueError("server_opt_step: the operands must be on the GPU")
+    if P:
+        rc = _C.server_opt_step(_p(theta), _p(target), _p(m), _p(v), _p(x_out), P, ref.SERVER_OPT_RULES.index(rule), lr,
+                                beta1, float(c1), beta2, float(c2), tau, _s())
+        if rc != 0:
+            raise ValueError(f"server_opt_step: the launch was refused (rule {rule!r}, P = {P})")
+    return theta
+
+
 def mix_rows(x, w, out_dtype=BF16):
     """[M, P] = W[M, K] · x[K, P]: subset models for Shapley utilities, emitted in the eval
     compute dtype (bf16 or fp32) by one native pass that reads each x row once per 32 models;

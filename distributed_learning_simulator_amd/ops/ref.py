@@ -714,6 +714,117 @@ def gaussian_add(acc, std, seed, stream, mask=None):
     return acc
 
 
+SERVER_OPT_RULES = ("sgdm", "adagrad", "adam", "yogi")  # the kernel's rule index is the position here
+
+
+def check_server_opt(rule, lr, beta1, beta2, tau) -> tuple[str, float, float, float, float]:
+    """(rule, lr, β1, β2, τ) of `server_opt_step` as a rule name and python floats; ValueError on a rule
+    that does not exist, a non-finite number, β outside [0, 1) or, for the adaptive rules, τ ≤ 0."""
+    if rule not in SERVER_OPT_RULES:
+        raise ValueError(f"server_opt_step: unknown rule {rule!r}; one of {SERVER_OPT_RULES}")
+    try:
+        lr, beta1, beta2, tau = float(lr), float(beta1), float(beta2), float(tau)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"server_opt_step: lr, beta1, beta2 and tau must be numbers ({e})") from e
+    if not math.isfinite(lr):
+        raise ValueError(f"server_opt_step: lr must be finite, got {lr}")
+    for name, b in (("beta1", beta1), ("beta2", beta2)):
+        if not 0.0 <= b < 1.0:  # (false for NaN too)
+            raise ValueError(f"server_opt_step: {name} must lie in [0, 1), got {b}")
+    if not math.isfinite(tau) or (rule != "sgdm" and not tau > 0.0):
+        raise ValueError(f"server_opt_step: tau must be finite and, for the adaptive rules, positive; got {tau}")
+    return rule, lr, beta1, beta2, tau
+
+
+def check_server_opt_operands(theta, target, m, v, rule, x_out=None) -> int:
+    """P of the operands of `server_opt_step`; ValueError on a wrong dtype, shape, stride or alignment
+    (both backends call this before they touch anything)."""
+    if theta.dtype != torch.float32 or theta.dim() != 1 or not theta.is_contiguous():
+        raise ValueError("server_opt_step: theta must be a contiguous fp32 vector")
+    P = theta.numel()
+    if P % 4:
+        raise ValueError(f"server_opt_step: P must be a multiple of 4, got {P}")
+    if theta.data_ptr() % 16:
+        raise ValueError("server_opt_step: theta must be 16-B aligned")
+    if (v is None) != (rule == "sgdm"):
+        raise ValueError("server_opt_step: v is None for sgdm and an fp64 [P] tensor for the adaptive rules")
+    for name, t, exact in (("target", target, False), ("m", m, True), ("v", v, True), ("x_out", x_out, True)):
+        if t is None and name in ("v", "x_out"):
+            continue
+        if t is None or t.dtype != torch.float64 or t.dim() != 1 or not t.is_contiguous() or t.device != theta.device:
+            raise ValueError(f"server_opt_step: {name} must be a contiguous fp64 vector on theta's device")
+        if t.numel() != P if exact else t.numel() < P:
+            raise ValueError(f"server_opt_step: {name} has {t.numel()} elements for P = {P}")
+        if t.data_ptr() % 32:
+            raise ValueError(f"server_opt_step: {name} must be 32-B aligned")
+    return P
+
+
+def server_opt_step(theta, target, m, v, rule, lr, beta1, beta2, tau, c1, c2, x_out=None):
+    """One server optimiser step on the pseudo-gradient d = target − θ (`ops.fl.server_opt_step` states
+    the contract): θ fp32 [P], m and v fp64 [P] are updated in place, `target` fp64 [≥ P] is read-only,
+    the pre-cast fp64 x goes to `x_out` if given. Every line below is one fp64 operation rounded once;
+    sqrt is numpy's (correctly rounded; the CPU `torch.sqrt` is not in every build), and so is the cast
+    to fp32 (round to nearest even, overflow to ±inf). The oracle of csrc/server_opt.hip and the CPU
+    path. c1 = 1 − β1 and c2 = 1 − β2 come from the caller, who forms them once for both backends."""
+    import numpy as np
+
+    rule, lr, beta1, beta2, tau = check_server_opt(rule, lr, beta1, beta2, tau)
+    P = check_server_opt_operands(theta, target, m, v, rule, x_out)
+    if P == 0:
+        return theta
+    if theta.device.type != "cpu":  # (the forced torch backend on a device: step on the host, copy back)
+        dev = [theta, m, v, x_out]
+        host = [None if t is None else t.cpu() for t in dev]
+        server_opt_step(host[0], target[:P].cpu(), host[1], host[2], rule, lr, beta1, beta2, tau, c1, c2, host[3])
+        for t, h in zip(dev, host):
+            if t is not None:
+                t.copy_(h)
+        return theta
+    c1, c2 = float(c1), float(c2)
+    with np.errstate(all="ignore"):
+        th32 = theta.numpy()  # (shares memory: the in-place writes below reach the tensors)
+        th = th32.astype(np.float64)
+        t = target[:P].numpy()
+        mm = m.numpy()
+        d = t - th
+        ok = np.isfinite(d)
+        q = d * d
+        m1 = beta1 * mm
+        if rule == "sgdm":
+            m1 = m1 + d
+        else:
+            g1 = c1 * d
+            m1 = m1 + g1
+            vv = v.numpy()
+            if rule == "adagrad":
+                v1 = vv + q
+            elif rule == "adam":
+                v1 = beta2 * vv
+                g2 = c2 * q
+                v1 = v1 + g2
+            else:
+                g2 = c2 * q
+                z = vv - q
+                sign = (z > 0.0).astype(np.float64) - (z < 0.0).astype(np.float64)  # (0 for z == 0 and NaN)
+                g2 = g2 * sign
+                v1 = vv - g2
+        step = lr * m1
+        if rule != "sgdm":
+            den = np.sqrt(v1)
+            den = den + tau
+            step = step / den
+        x = th + step
+        x = np.where(ok, x, t)  # a non-finite d: θ' = fl32(target), the state keeps its bits
+        if x_out is not None:
+            x_out.numpy()[...] = x
+        th32[...] = x.astype(np.float32)
+        np.copyto(mm, m1, where=ok)
+        if rule != "sgdm":
+            np.copyto(vv, v1, where=ok)
+    return theta
+
+
 def krum_scores(D, f: int):
     """(scores [n] fp64, f actually used): the Krum score of row i is the sum of its k = clamp(n − f −
     2, 1, n − 1) smallest D[i, j], j ≠ i, added in ascending order in fp64 from +0.0; a non-finite

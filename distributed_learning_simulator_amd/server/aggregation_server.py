@@ -22,6 +22,7 @@ import torch
 from ..message import FlatParameterMessage, Message
 from ..utils.logging import get_logger
 from .server import Server
+from .server_optimizer import ServerOptimizer
 
 
 class AggregationServer(Server):
@@ -38,6 +39,12 @@ class AggregationServer(Server):
         self.global_parameter: torch.Tensor | None = None
         self.selected: list[int] = []
         self.last_result = None
+        # the server's own optimiser step on the aggregated model (server_optimizer.py); None: θ_{t+1}
+        # is the aggregate itself
+        self.server_optimizer = ServerOptimizer.from_config(config)
+        if self.server_optimizer is not None and hasattr(self, "run_round"):
+            raise RuntimeError(f"{config.distributed_algorithm}: a method with its own round structure aggregates no "
+                               "dense model for a server optimiser to step on (algorithm_kwargs.server_optimizer)")
 
     @property
     def round_number(self) -> int:
@@ -48,6 +55,8 @@ class AggregationServer(Server):
               "selected": list(self.selected)}
         if self._algorithm is not None and hasattr(self._algorithm, "state_dict"):
             st["algorithm"] = self._algorithm.state_dict()
+        if self.server_optimizer is not None:
+            st["server_optimizer"] = self.server_optimizer.state_dict()
         return st
 
     def load_state_dict(self, state: dict) -> None:
@@ -57,6 +66,8 @@ class AggregationServer(Server):
         self.selected = list(state.get("selected", []))
         if "algorithm" in state and self._algorithm is not None and hasattr(self._algorithm, "load_state_dict"):
             self._algorithm.load_state_dict(state["algorithm"])
+        if "server_optimizer" in state and self.server_optimizer is not None:
+            self.server_optimizer.load_state_dict(state["server_optimizer"])
 
     @property
     def performance_stat(self) -> dict:
@@ -88,7 +99,14 @@ class AggregationServer(Server):
                                             save_dir=self.save_dir)
 
     def _aggregate_worker_data(self) -> Message:
-        return self._algorithm.aggregate_worker_data(self.global_parameter)
+        result = self._algorithm.aggregate_worker_data(self.global_parameter)
+        opt = self.server_optimizer
+        if opt is None:
+            return result
+        active = getattr(self.session, "round_active", None)
+        if active is not None and len(active) == 0:
+            return result  # everyone failed: θ_t stays, and so do m, v and the step count
+        return opt.step(self.global_parameter, result, self._algorithm)
 
     # ------------------------------------------------------------ send result
     def _before_send_result(self, result: Message) -> None:

@@ -37,6 +37,7 @@ from .models.zoo import build_model, stored_image_channels
 from .parallel.comm import Comm, get_comm, init_distributed
 from .practitioner import create_practitioners
 from .sampler import get_partition
+from .server.server_optimizer import state_bytes as server_optimizer_bytes
 from .utils.logging import get_logger
 from .utils.tracing import Watchdog, round_timeout, trace
 
@@ -128,6 +129,7 @@ class Session:
             plan = getattr(CentralizedAlgorithmFactory.config[cfg.distributed_algorithm]["client_cls"],
                            "memory_plan", None)
             extra_rows, reserved = plan(cfg, self.layout) if plan is not None else (0, 0)
+            reserved += server_optimizer_bytes(cfg, self.layout)  # the server optimiser's fp64 state, if any
             capacity = plan_capacity(per_rank, self.layout, self.model, self.dc, self.hyper, self.device,
                                      self.compute_dtype, explicit=cfg.cohort_size,
                                      fraction=0.2 if cfg.limited_resource else 0.8, extra_rows=extra_rows,

@@ -40,5 +40,12 @@ $S --config-name fed_scaffold/mnist.yaml ++fed_scaffold.round=2 ++fed_scaffold.e
    ++fed_scaffold.debug=True
 $S --config-name fed_dp_avg/mnist.yaml ++fed_dp_avg.round=2 ++fed_dp_avg.epoch=1 ++fed_dp_avg.worker_number=4 \
    ++fed_dp_avg.algorithm_kwargs.dp_clip_norm=0.05 ++fed_dp_avg.debug=True
+# server optimisers on the aggregated pseudo-gradient (FedAvgM, FedAdagrad, FedAdam, FedYogi); two rounds,
+# so that the second steps on non-zero state; and the same stage behind another aggregator
+for M in fed_avgm fed_adagrad fed_adam fed_yogi; do
+  $S --config-name $M/mnist.yaml ++$M.round=2 ++$M.epoch=1 ++$M.worker_number=4 ++$M.debug=True
+done
+$S --config-name fed_median/mnist.yaml ++fed_median.round=2 ++fed_median.epoch=1 ++fed_median.worker_number=4 \
+   ++fed_median.algorithm_kwargs.server_optimizer=adam ++fed_median.debug=True
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
