@@ -581,6 +581,29 @@ int server_opt_max_blocks();
 int server_opt_step(float* theta, const double* target, double* m, double* v, double* x, long P, int rule, double lr,
                     double beta1, double c1, double beta2, double c2, double tau, hipStream_t s);
 
+// ---- pairwise-masked secure aggregation (csrc/secagg.hip, ops/ref.py secagg_mask_rows / ring_sum / ring_unmask)
+// Mask word w(κ, p): word p % 4 of Philox4x32-10 with key (κ lo, κ hi), counter (p/4 lo, p/4 hi, 0, 0x53413031).
+// secagg_mask_rows: out[k][p] (int32, row stride ldo) = low 32 bits of rint(double(clamp(x[k][p], −R, R))·2^f)
+// (NaN → 0) + Σ_e signs[e]·w(keys[e], p) over e in [off[k], off[k + 1]); stats [K][2] int32 = (elements with
+// |x| > R, NaNs) per row, zeroed here first. x [K][P] fp32 (row stride ldx), rows 16-B aligned, P % 4 == 0, K ≤
+// SECAGG_MAX_ROWS; out may be x. ring_sum: acc[p] (int64, 16-B aligned) += Σ_k (int64) rows[k][p]. ring_unmask:
+// acc[p] −= Σ_e signs[e]·(int64) w(keys[e], p), E ≤ SECAGG_MAX_ROWS². `variant`: the ILP form of the expander
+// (groups of four elements per lane × entries per loop trip); all give the same bits. All return 0, or −1
+// (nothing launched) for operands that break the above. secagg_mask_span: the elements of a row that one
+// full grid of the mask kernel covers (beyond it a lane takes another trip).
+#define SECAGG_MAX_ROWS 512
+#define SECAGG_VARIANT_G1U1 1
+#define SECAGG_VARIANT_G2U1 2
+#define SECAGG_VARIANT_G1U2 3
+#define SECAGG_VARIANT_DEFAULT SECAGG_VARIANT_G1U2
+long secagg_mask_span(int variant);
+int secagg_mask_rows(const float* x, long ldx, int* out, long ldo, int K, long P, const int* off,
+                     const unsigned long long* keys, const int* signs, float R, int frac_bits, int* stats, int variant,
+                     hipStream_t s);
+int ring_sum(const int* rows, long ld, int K, long P, long long* acc, hipStream_t s);
+int ring_unmask(long long* acc, long P, const unsigned long long* keys, const int* signs, int E, int variant,
+                hipStream_t s);
+
 // out[k][r][c] = keep(k, r, c) ? x·scale : 0 over [K][rows][N] (row stride ld), the dropout rule of
 // the GEMM epilogue; seeds [K]. f32: fp32 (else bf16) tensors.
 void dropout_apply(const void* x, void* out, int K, long rows, int N, long ld, const uint32_t* seeds, float p,

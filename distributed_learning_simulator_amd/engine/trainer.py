@@ -609,11 +609,17 @@ class CohortTrainer:
                 # the eager step's cached blocks go back to the driver so the graph's private pool
                 # can take them (else activation memory is held twice)
                 torch.cuda.synchronize(self.device)
+                # dead cycles of older sessions (their tensors, streams, graphs) are finalised HERE, on
+                # an idle device: torch.cuda.graph no longer collects on entry (it does only under
+                # torch.compiler.config.force_cudagraph_gc), and a collection deferred by the
+                # gc.disable() below would otherwise start at the first allocation after gc.enable()
+                # and destroy their streams between this graph's capture and its first launch
+                gc.collect()
                 torch.cuda.empty_cache()
                 g = torch.cuda.CUDAGraph()
                 # no cyclic GC while capturing: a collected cycle holding an older session's graph
-                # or tensors would free device memory inside the capture (HIP aborts);
-                # torch.cuda.graph collects once on entry
+                # or tensors would free device memory inside the capture (HIP aborts); nor before the
+                # first replay has been launched
                 gc_was_enabled = gc.isenabled()
                 gc.disable()
                 try:
@@ -621,11 +627,11 @@ class CohortTrainer:
                     # on their own streams) keep running while this one captures
                     with torch.cuda.graph(g, capture_error_mode="thread_local"):
                         run_parts()
+                    sg.graph = g
+                    g.replay()
                 finally:
                     if gc_was_enabled:
                         gc.enable()
-            sg.graph = g
-            g.replay()
 
     def _train_graphed(self, schedule: RoundSchedule, parts, executor, stats: TrainStats,
                        epoch_base: int) -> TrainStats:

@@ -45,6 +45,7 @@ FILE_FLAGS = {"compress.hip": ["-ffp-contract=on"],
               # server_opt.hip: β·m, c·d, c·q, lr·m' and the sums that follow them are rounded separately
               # (the contract of ops/ref.py server_opt_step, where each is its own statement)
               "server_opt.hip": ["-ffp-contract=off"]}
+# (secagg.hip needs no entry: integer arithmetic in Z_{2^32}, and its one fp64 product, t · 2^f, is exact)
 
 
 def _headers() -> list[str]:

@@ -25,6 +25,9 @@ Codes:
 - NNADQ (FedOBD): round-to-nearest with the per-tensor adaptive bit-width of `quant.nnadq_bits`.
 
 x̂ = lo + q·scale; the CPU path below writes the identical buffer and decodes to identical bits.
+
+`MaskedPayload` (fed_secagg, csrc/secagg.hip) carries the masked fixed-point rows of secure aggregation:
+int32 words that only add up (`accumulate` into an int64 ring accumulator); there is no dense form to decode.
 """
 
 from __future__ import annotations
@@ -354,3 +357,31 @@ def pack_topk_ef(delta: torch.Tensor, err: torch.Tensor, meta: LayoutMeta, k: in
 
     idx, val = hip.topk_pack(delta, err, meta, k)
     return SparsePayload(idx, val, meta, k)
+
+
+# ------------------------------------------------------------------ masked uploads (secure aggregation)
+@dataclass
+class MaskedPayload:
+    """The uploads of K clients after `ops.fl.secagg_mask_rows`: int32 [K, P] words of Z_{2^32} (the memory of
+    the delta rows they replaced). `wire` holds each client's bytes: the masked vector plus the protocol's
+    key and share traffic (utils/secagg_protocol.py)."""
+
+    rows: torch.Tensor  # int32 [K, P], row stride >= P
+    wire: list
+
+    @property
+    def K(self) -> int:
+        return self.rows.shape[0]
+
+    def row_bytes(self) -> list[int]:
+        return [int(b) for b in self.wire]
+
+    def decode(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        raise RuntimeError("a masked upload has no dense form: only the sum of a round's uploads can be unmasked")
+
+    def accumulate(self, acc: torch.Tensor, w: torch.Tensor | None = None) -> None:
+        """acc [P] int64 += Σ_k rows[k] (unweighted: a weight would have to be applied before masking)."""
+        from .fl import ring_sum
+
+        assert w is None, "masked uploads are added unweighted"
+        ring_sum(self.rows, acc)

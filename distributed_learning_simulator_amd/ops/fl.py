@@ -14,6 +14,8 @@
 | clipped_sum          | — (DP-FedAvg clipped fp64 accumulation)                          |
 | gaussian_add         | — (DP-FedAvg Gaussian mechanism, Philox4x32-10 + Box-Muller)     |
 | server_opt_step      | — (FedAvgM / FedAdagrad / FedAdam / FedYogi server step, Reddi 2021)|
+| secagg_mask_rows     | — (secure aggregation: fixed-point upload + pairwise masks, Bonawitz 2017) |
+| ring_sum / ring_unmask / ring_decode | — (secure aggregation: the server's Z_{2^32} sum and unmasking) |
 | mix_rows             | Shapley subset models (K8, `aggregation_algorithm.py:30-50`)   |
 | masked_weighted_sum  | FedDropoutAvg aggregation (K10, `fed_dropout_avg/algorithm.py`)|
 | dropout_mask         | FedDropoutAvg Bernoulli mask (K9, `fed_dropout_avg/worker.py`) |
@@ -247,6 +249,73 @@ def server_opt_step(theta, target, m, v, rule, lr, beta1=0.9, beta2=0.99, tau=1e
     rule, lr, beta1, beta2, tau = ref.check_server_opt(rule, lr, beta1, beta2, tau)
     c1, c2 = 1.0 - beta1, 1.0 - beta2
     return backend.get(theta).server_opt_step(theta, target, m, v, rule, lr, beta1, beta2, tau, c1, c2, x_out)
+
+
+def secagg_frac_bits(R, m: int, f=None):
+    """(R as fp32, f): the fixed-point code of secure aggregation for the range R and the fixed cohort size m.
+    R must be finite and > 0 (rounded to fp32 once; the bound uses the rounded value). f is the given
+    `f`, else the largest integer with m · R · 2^f ≤ 2^31 − 1. ValueError if a given f breaks that bound,
+    or if f would be below 1."""
+    return ref.secagg_frac_bits(R, m, f)
+
+
+def secagg_mask_words(key: int, P: int, start: int = 0, device=None):
+    """int64 [P]: the mask words w(κ, p) for p = start .. start + P − 1, unsigned 32-bit values. For the
+    Philox call index i = p // 4, w(κ, p) is word p % 4 of Philox4x32-10 with key (κ & 0xffffffff, κ >> 32)
+    and counter (i & 0xffffffff, i >> 32, 0, 0x53413031). w depends on (κ, p) alone. (torch; the kernels
+    expand the same stream in registers.)"""
+    return ref.secagg_mask_words(key, P, start, device)
+
+
+def secagg_mask_rows(x, entries, R, f: int, out=None, variant: int | None = None):
+    """The masked upload of secure aggregation (Bonawitz et al. 2017): (out int32 [K, P], stats int32 [K, 2]).
+
+    x: fp32 [K, P], row stride ≥ P, rows 16-B aligned, P % 4 == 0, 1 ≤ K ≤ 512. entries = (offsets, keys,
+    signs): row k owns the entries offsets[k] .. offsets[k + 1] − 1 of the flat lists keys (unsigned 64-bit
+    python ints κ) and signs (+1 / −1); a row may have none, at most 512. R, f: `secagg_frac_bits` with the
+    op's own bound R · 2^f ≤ 2^31 − 1.
+
+      q(x)      t = x clamped to [−R, R] in fp32 (±inf clamp to ±R); q = rint(fl64(t) · 2^f), ties to even.
+                Scaling by a power of two is exact in fp64: one rounding. A NaN gives q = 0.
+      w(κ, p)   `secagg_mask_words`.
+      out[k, p] = the low 32 bits of q(x[k, p]) + Σ_e sign_e · w(κ_e, p), read as int32.
+      stats[k]  = (elements with |x| > R, infinities included; NaN elements).
+
+    `out` may be the memory of x (x.view(torch.int32)): the upload overwrites the delta rows. Masks are
+    drawn at every position of the padded layout; padding holds x = 0 and cancels like everything else.
+    All of it is integer arithmetic in Z_{2^32}: no summation order, no contraction flag, no tolerance —
+    the kernel (csrc/secagg.hip) and the oracle (`ops.ref.secagg_mask_rows`, also the CPU path) give the
+    same integers. `variant` selects another ILP form of the kernel's expander (benchmarks): same bits.
+    A wrong dtype, shape, stride, alignment or entry table raises ValueError before anything is written."""
+    offsets, keys, signs = entries
+    be = backend.get(x)
+    if be is ref:
+        return ref.secagg_mask_rows(x, offsets, keys, signs, R, f, out)
+    return be.secagg_mask_rows(x, offsets, keys, signs, R, f, out, variant)
+
+
+def ring_sum(rows, acc):
+    """acc (int64 [P], 16-B aligned) [p] += Σ_k (int64) rows[k, p] over int32 rows [K, P] (row stride ≥ P,
+    sign-extended). With K ≤ 512 rows a call there is no int64 overflow and the low 32 bits are the sum
+    in Z_{2^32}: exact, so any order and any split over calls or ranks gives the same bits. Returns acc."""
+    return backend.get(acc).ring_sum(rows, acc)
+
+
+def ring_unmask(acc, entries, variant: int | None = None):
+    """acc (int64 [P]) [p] −= Σ_e sign_e · (int64) w(κ_e, p) over one flat entry list entries = (keys, signs)
+    of at most 512 · 512 entries (no overflow): the server's removal of the self masks of the clients
+    that reported and of the pair masks of those that dropped. Returns acc."""
+    keys, signs = entries
+    be = backend.get(acc)
+    if be is ref:
+        return ref.ring_unmask(acc, keys, signs)
+    return be.ring_unmask(acc, keys, signs, variant)
+
+
+def ring_decode(acc, f: int):
+    """fp64 [P]: v · 2^−f, v = the low 32 bits of acc[p] as a signed int32 — exact. P-sized, once a round:
+    torch elementwise on both backends."""
+    return ref.ring_decode(acc, f)
 
 
 def mix_rows(x, w, out_dtype):

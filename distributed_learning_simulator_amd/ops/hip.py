@@ -1828,6 +1828,67 @@ def server_opt_step(theta, target, m, v, rule, lr, beta1, beta2, tau, c1, c2, x_
     return theta
 
 
+def secagg_default_variant() -> int:
+    return int(_C.secagg_default_variant())
+
+
+def secagg_mask_span(variant: int | None = None) -> int:
+    """Elements of a row that one full grid of the mask kernel covers; past it a lane takes another trip."""
+    return int(_C.secagg_mask_span(secagg_default_variant() if variant is None else int(variant)))
+
+
+def _secagg_entries(keys, signs, device):
+    k = torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in keys], dtype=torch.int64).to(device)
+    return k, torch.tensor(signs, dtype=torch.int32).to(device)
+
+
+def secagg_mask_rows(x, offsets, keys, signs, R, f, out=None, variant=None):
+    """csrc/secagg.hip: (out int32 [K, P], stats int32 [K, 2]) by the arithmetic of `ops.ref.secagg_mask_rows`;
+    `out` may be x.view(torch.int32). Operand errors raise ValueError before the launch."""
+    K, P, offsets, keys, signs = ref.check_secagg_rows(x, out, offsets, keys, signs)
+    R, f = ref.secagg_frac_bits(R, 1, f)
+    if not x.is_cuda:
+        raise ValueError("secagg_mask_rows: the operands must be on the GPU")
+    if out is None:
+        out = torch.empty((K, P), dtype=torch.int32, device=x.device)
+    stats = torch.empty((K, 2), dtype=torch.int32, device=x.device)
+    off = torch.tensor(offsets, dtype=torch.int32).to(x.device)
+    kd, sd = _secagg_entries(keys, signs, x.device)
+    variant = secagg_default_variant() if variant is None else int(variant)
+    rc = _C.secagg_mask_rows(_p(x), x.stride(0) if K > 1 else P, _p(out), out.stride(0) if K > 1 else P, K, P, _p(off),
+                             _p(kd), _p(sd), R, f, _p(stats), variant, _s())
+    if rc != 0:
+        raise ValueError(f"secagg_mask_rows: the launch was refused (K = {K}, P = {P}, f = {f}, variant {variant})")
+    return out, stats
+
+
+def ring_sum(rows, acc):
+    """csrc/secagg.hip: acc (int64 [P]) += Σ_k (int64) rows[k, :]."""
+    P = ref.check_ring_operands(acc, rows)
+    if not acc.is_cuda:
+        raise ValueError("ring_sum: the operands must be on the GPU")
+    K = rows.shape[0]
+    if P and _C.ring_sum(_p(rows), rows.stride(0) if K > 1 else P, K, P, _p(acc), _s()) != 0:
+        raise ValueError(f"ring_sum: the launch was refused (K = {K}, P = {P})")
+    return acc
+
+
+def ring_unmask(acc, keys, signs, variant=None):
+    """csrc/secagg.hip: acc (int64 [P]) −= Σ_e signs[e] · w(keys[e], :)."""
+    P = ref.check_ring_operands(acc)
+    keys, signs = ref.check_secagg_entries(keys, signs)
+    if len(keys) > ref.SECAGG_MAX_ROWS ** 2:
+        raise ValueError(f"ring_unmask: at most {ref.SECAGG_MAX_ROWS ** 2} entries, got {len(keys)}")
+    if not acc.is_cuda:
+        raise ValueError("ring_unmask: the operands must be on the GPU")
+    if P and keys:
+        kd, sd = _secagg_entries(keys, signs, acc.device)
+        variant = secagg_default_variant() if variant is None else int(variant)
+        if _C.ring_unmask(_p(acc), P, _p(kd), _p(sd), len(keys), variant, _s()) != 0:
+            raise ValueError(f"ring_unmask: the launch was refused (P = {P}, {len(keys)} entries)")
+    return acc
+
+
 def mix_rows(x, w, out_dtype=BF16):
     """[M, P] = W[M, K] · x[K, P]: subset models for Shapley utilities, emitted in the eval
     compute dtype (bf16 or fp32) by one native pass that reads each x row once per 32 models;

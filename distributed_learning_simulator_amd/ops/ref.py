@@ -679,6 +679,18 @@ def philox4x32(counter, key, rounds: int = 10):
     return c0, c1, c2, c3
 
 
+def philox4x32_int(counter, key, rounds: int = 10) -> tuple[int, int, int, int]:
+    """`philox4x32` for one counter of four python ints: the same words as python ints, without a tensor
+    (the host-side protocol of secure aggregation draws thousands of single values a round)."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+    k0, k1 = int(key[0]) & _M32, int(key[1]) & _M32
+    for _ in range(rounds):
+        p0, p1 = PHILOX_M0 * c0, PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + PHILOX_W0) & _M32, (k1 + PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
 def gaussian_noise(P: int, seed: int, stream: int, start: int = 0, device=None):
     """fp64 [P] standard normal draws z[start], ..., z[start + P − 1] of the (seed, stream) sequence:
     for the pair index i = p // 2, Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
@@ -712,6 +724,206 @@ def gaussian_add(acc, std, seed, stream, mask=None):
     m = mask != 0
     acc[m] = acc[m] + t[m]
     return acc
+
+
+# ------------------------------------------------------------------ pairwise-masked secure aggregation
+SECAGG_TAG = 0x53413031  # fourth counter word of the mask streams ("SA01")
+SECAGG_MAX_ROWS = 512  # csrc/dls.h
+_SECAGG_CHUNK = 1 << 20  # Philox calls per vectorised step of the oracle
+
+
+def secagg_frac_bits(R, m: int, f=None) -> tuple[float, int]:
+    """(R as the fp32 value the clamp uses, f) of the fixed-point code of `secagg_mask_rows`. R must be a
+    finite number > 0 (it is rounded to fp32 once, and the bound below uses the rounded value); m ≥ 1 is the
+    fixed cohort size. f = `f` if given, else the largest integer with m · R · 2^f ≤ 2^31 − 1, so that the sum
+    of m codes cannot wrap. ValueError if a given f breaks that bound or is below 1, or if the computed f is
+    below 1."""
+    from fractions import Fraction
+
+    try:
+        R = float(R)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"secagg: the range must be a number ({e})") from e
+    if not (R > 0.0 and math.isfinite(R)):
+        raise ValueError(f"secagg: the range must be a finite positive number, got {R}")
+    R = float(torch.tensor(R, dtype=torch.float32))
+    m = int(m)
+    if not (R > 0.0 and math.isfinite(R)) or m < 1:
+        raise ValueError(f"secagg: range {R} (as fp32) and cohort size {m} must be positive and finite")
+    room = Fraction(2 ** 31 - 1) / (Fraction(R) * m)
+    if f is None:
+        f = 0
+        while Fraction(2) ** (f + 1) <= room:
+            f += 1
+        if f < 1:
+            raise ValueError(f"secagg: no fixed-point code with >= 1 fractional bit fits m = {m}, R = {R} in 2^31")
+        return R, f
+    if isinstance(f, bool) or int(f) != f:
+        raise ValueError(f"secagg: frac_bits must be an integer, got {f!r}")
+    f = int(f)
+    if f < 1 or Fraction(2) ** f > room:
+        raise ValueError(f"secagg: frac_bits = {f} overflows the ring: m * R * 2^f must stay <= 2^31 - 1 "
+                         f"(m = {m}, R = {R}) with f >= 1")
+    return R, f
+
+
+def _philox_keys(i, k0, k1):
+    """Philox4x32-10 with counter (i lo, i hi, 0, SECAGG_TAG) for int64 tensors i, k0, k1 that broadcast."""
+    c0, c1, c2, c3 = i & _M32, i >> 32, torch.zeros_like(i), torch.full_like(i, SECAGG_TAG)
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(PHILOX_M0, c0)
+        hi1, lo1 = _mulhilo32(PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + PHILOX_W0) & _M32, (k1 + PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def secagg_mask_words(key: int, P: int, start: int = 0, device=None):
+    """int64 [P] holding the unsigned 32-bit mask words w(κ, p), p = start .. start + P − 1: word p % 4 of
+    Philox4x32-10 with key (κ & 0xffffffff, κ >> 32) and counter (i & 0xffffffff, i >> 32, 0, 0x53413031), i =
+    p // 4. w depends on (κ, p) alone."""
+    key = int(key) & 0xFFFFFFFFFFFFFFFF
+    first, last = start // 4, (start + P + 3) // 4
+    i = torch.arange(first, max(last, first), dtype=torch.int64, device=device)
+    k0 = torch.full_like(i, key & _M32)
+    w = torch.stack(_philox_keys(i, k0, torch.full_like(i, key >> 32)), dim=1).reshape(-1)
+    return w[start - 4 * first : start - 4 * first + P]
+
+
+def check_secagg_entries(keys, signs) -> tuple[list[int], list[int]]:
+    keys, signs = [int(k) for k in keys], [int(s) for s in signs]
+    if len(keys) != len(signs):
+        raise ValueError(f"secagg: {len(keys)} keys for {len(signs)} signs")
+    if any(s not in (1, -1) for s in signs):
+        raise ValueError("secagg: every sign is +1 or -1")
+    if any(not 0 <= k < 2 ** 64 for k in keys):
+        raise ValueError("secagg: every key is an unsigned 64-bit integer")
+    return keys, signs
+
+
+def secagg_mask_sum(keys, signs, P: int, device=None):
+    """int64 [P]: Σ_e signs[e] · w(keys[e], p) as an exact signed sum (|·| < 2^32 · len(keys))."""
+    keys, signs = check_secagg_entries(keys, signs)
+    assert P % 4 == 0
+    n4 = P // 4
+    total = torch.zeros(P, dtype=torch.int64, device=device)
+    if not keys or not P:
+        return total
+    i = torch.arange(n4, dtype=torch.int64, device=device)[None, :]
+    step = max(1, _SECAGG_CHUNK // n4)
+    for e0 in range(0, len(keys), step):
+        ks = keys[e0 : e0 + step]
+        k0 = torch.tensor([k & _M32 for k in ks], dtype=torch.int64, device=device)[:, None]
+        k1 = torch.tensor([k >> 32 for k in ks], dtype=torch.int64, device=device)[:, None]
+        sg = torch.tensor(signs[e0 : e0 + step], dtype=torch.int64, device=device)[:, None, None]
+        w = torch.stack(_philox_keys(i, k0, k1), dim=2)  # [entries, P / 4, 4]
+        total += (w * sg).sum(0).reshape(-1)
+    return total
+
+
+def secagg_quantise(x, R: float, f: int):
+    """(q int64 [K, P], stats int32 [K, 2]) of fp32 rows x: t = x clamped to [−R, R] in fp32 (±inf clamp to
+    ±R), q = rint(fl64(t) · 2^f) with ties to even — the scaling is exact in fp64, so this is the only
+    rounding — and q = 0 for a NaN. stats[k] = (elements with |x| > R, infinities included; NaN elements)."""
+    assert x.dtype == torch.float32 and x.dim() == 2
+    nan = torch.isnan(x)
+    t = torch.clamp(torch.where(nan, torch.zeros_like(x), x), min=-R, max=R)
+    q = torch.round(t.double() * float(2 ** f)).to(torch.int64)
+    stats = torch.stack([(x.abs() > R).sum(1), nan.sum(1)], dim=1).to(torch.int32)
+    return q, stats
+
+
+def check_secagg_rows(x, out, offsets, keys, signs):
+    """(K, P, offsets, keys, signs) of the operands of `secagg_mask_rows`; ValueError on a wrong dtype,
+    shape, stride, alignment, entry table or row count (both backends call this before they touch anything)."""
+    if x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("secagg_mask_rows: x must be fp32 [K, P] with unit column stride")
+    K, P = x.shape
+    if not 1 <= K <= SECAGG_MAX_ROWS:
+        raise ValueError(f"secagg_mask_rows supports 1 to {SECAGG_MAX_ROWS} rows, got {K}")
+    if P % 4:
+        raise ValueError(f"secagg_mask_rows: P must be a multiple of 4, got {P}")
+    for name, t in (("x", x), ("out", out)):
+        if t is None:
+            continue
+        if name == "out" and (t.dtype != torch.int32 or t.shape != (K, P) or (P > 1 and t.stride(1) != 1)
+                              or t.device != x.device):
+            raise ValueError(f"secagg_mask_rows: out must be int32 [{K}, {P}] with unit column stride on x's device")
+        if t.data_ptr() % 16 or (K > 1 and (t.stride(0) % 4 or t.stride(0) < P)):
+            raise ValueError(f"secagg_mask_rows: the rows of {name} must be 16-B aligned and must not overlap")
+    if out is not None and out.data_ptr() == x.data_ptr() and K > 1 and out.stride(0) != x.stride(0):
+        raise ValueError("secagg_mask_rows: an in-place out must have x's row stride")
+    offsets = [int(o) for o in offsets]
+    keys, signs = check_secagg_entries(keys, signs)
+    if len(offsets) != K + 1 or offsets[0] != 0 or offsets[-1] != len(keys) or any(
+            a > b for a, b in zip(offsets, offsets[1:])):
+        raise ValueError(f"secagg_mask_rows: offsets must be {K + 1} ascending entry indices from 0 to {len(keys)}")
+    if any(b - a > SECAGG_MAX_ROWS for a, b in zip(offsets, offsets[1:])):
+        raise ValueError(f"secagg_mask_rows: at most {SECAGG_MAX_ROWS} entries per row")
+    return K, P, offsets, keys, signs
+
+
+def _to_int32(v):
+    """The low 32 bits of int64 values as signed int32."""
+    v = v & _M32
+    return torch.where(v >= 2 ** 31, v - 2 ** 32, v).to(torch.int32)
+
+
+def secagg_mask_rows(x, offsets, keys, signs, R, f, out=None):
+    """The masked upload (`ops.fl.secagg_mask_rows` states the contract; the oracle of csrc/secagg.hip and the
+    CPU path): (out int32 [K, P], stats int32 [K, 2]) with out[k, p] = the low 32 bits of q(x[k, p]) + Σ_e
+    sign_e · w(κ_e, p) over the entries offsets[k] .. offsets[k + 1] − 1 of row k. `out` may alias x."""
+    K, P, offsets, keys, signs = check_secagg_rows(x, out, offsets, keys, signs)
+    R, f = secagg_frac_bits(R, 1, f)
+    q, stats = secagg_quantise(x, R, f)
+    for k in range(K):
+        a, b = offsets[k], offsets[k + 1]
+        q[k] += secagg_mask_sum(keys[a:b], signs[a:b], P, device=x.device)
+    res = _to_int32(q)
+    if out is None:
+        return res, stats
+    out.copy_(res)
+    return out, stats
+
+
+def check_ring_operands(acc, rows=None) -> int:
+    if acc.dtype != torch.int64 or acc.dim() != 1 or not acc.is_contiguous() or acc.data_ptr() % 16:
+        raise ValueError("ring: acc must be a contiguous, 16-B aligned int64 vector")
+    P = acc.numel()
+    if P % 4:
+        raise ValueError(f"ring: P must be a multiple of 4, got {P}")
+    if rows is not None:
+        if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != P or (P > 1 and rows.stride(1) != 1):
+            raise ValueError(f"ring_sum: rows must be int32 [K, {P}] with unit column stride")
+        K = rows.shape[0]
+        if not 1 <= K <= SECAGG_MAX_ROWS:
+            raise ValueError(f"ring_sum supports 1 to {SECAGG_MAX_ROWS} rows, got {K}")
+        if rows.device != acc.device or rows.data_ptr() % 16 or (K > 1 and (rows.stride(0) % 4 or rows.stride(0) < P)):
+            raise ValueError("ring_sum: rows must be on acc's device, 16-B aligned and must not overlap")
+    return P
+
+
+def ring_sum(rows, acc):
+    """acc (int64 [P]) [p] += Σ_k (int64) rows[k, p] (sign-extended int32 rows, ≤ 512 of them: no int64
+    overflow; the low 32 bits are the sum in Z_{2^32}). Returns `acc`."""
+    check_ring_operands(acc, rows)
+    return acc.add_(rows.to(torch.int64).sum(0))
+
+
+def ring_unmask(acc, keys, signs):
+    """acc (int64 [P]) [p] −= Σ_e signs[e] · (int64) w(keys[e], p) over one flat entry list (≤ 512 · 512
+    entries: no overflow). Returns `acc`."""
+    P = check_ring_operands(acc)
+    keys, signs = check_secagg_entries(keys, signs)
+    if len(keys) > SECAGG_MAX_ROWS * SECAGG_MAX_ROWS:
+        raise ValueError(f"ring_unmask: at most {SECAGG_MAX_ROWS * SECAGG_MAX_ROWS} entries, got {len(keys)}")
+    return acc.sub_(secagg_mask_sum(keys, signs, P, device=acc.device))
+
+
+def ring_decode(acc, f: int):
+    """fp64 [P]: v · 2^−f with v = the low 32 bits of acc[p] as a signed int32 (exact)."""
+    assert acc.dtype == torch.int64
+    return _to_int32(acc).to(torch.float64) * (2.0 ** -int(f))
 
 
 SERVER_OPT_RULES = ("sgdm", "adagrad", "adam", "yogi")  # the kernel's rule index is the position here

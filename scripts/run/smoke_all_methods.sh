@@ -47,5 +47,12 @@ for M in fed_avgm fed_adagrad fed_adam fed_yogi; do
 done
 $S --config-name fed_median/mnist.yaml ++fed_median.round=2 ++fed_median.epoch=1 ++fed_median.worker_number=4 \
    ++fed_median.algorithm_kwargs.server_optimizer=adam ++fed_median.debug=True
+# secure aggregation (pairwise masks in Z_2^32): the complete graph, then a ring of degree 2 with a dropout
+# whose masks the server rebuilds from one share
+$S --config-name fed_secagg/mnist.yaml ++fed_secagg.round=2 ++fed_secagg.epoch=1 ++fed_secagg.worker_number=4 \
+   ++fed_secagg.debug=True
+$S --config-name fed_secagg/mnist.yaml ++fed_secagg.round=2 ++fed_secagg.epoch=1 ++fed_secagg.worker_number=6 \
+   ++fed_secagg.algorithm_kwargs.secagg_degree=2 ++fed_secagg.algorithm_kwargs.secagg_threshold=1 \
+   ++fed_secagg.algorithm_kwargs.failure_rate=0.2 ++fed_secagg.debug=True
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
