@@ -270,11 +270,16 @@ static bool use_mfma(int L, int DH) {
 
 bool attn_packed_supported(int L, int DH) { return use_mfma(L, DH); }
 
-bool attn_supported(int L, int DH) {
-  if (attn_mfma_supported(L, DH)) return true;
-  if (!(DH == 8 || DH == 16 || DH == 20 || DH == 32 || DH == 64)) return false;
+// What the VALU kernels run: their head dims (ATTN_DISPATCH) and a head whose staged rows — the
+// dK/dV kernel's Q, dO, lse and δ, the largest of the three — fit the CU's 160 KiB of LDS
+bool attn_valu_supported(int L, int DH) {
+  if (!(DH == 8 || DH == 16 || DH == 20 || DH == 32 || DH == 64) || L < 1) return false;
   return (2L * L * DH + 2L * L) * 4 <= 160L * 1024;
 }
+
+// true exactly when attn_fwd / attn_bwd (contiguous layout, no dropout) launch under the current
+// attn_mfma option
+bool attn_supported(int L, int DH) { return use_mfma(L, DH) || attn_valu_supported(L, DH); }
 
 #define DISPATCH_T(F32, ...) \
   if (F32) {                 \
@@ -294,7 +299,7 @@ bool attn_fwd(const void* q, const void* k, const void* v, const int* key_valid,
     return attn_fwd_mfma(q, k, v, key_valid, o, lse, KBH, H, L, DH, f32, s, ldqkv, ldo, drop_seeds, heads_per_client,
                          drop_p);
   if (ldqkv || ldo || drop_p > 0.f) return false;  // packed layouts / dropout: MFMA kernels only
-  if (!attn_supported(L, DH) || (2L * L * DH + 2L * L) * 4 > 160L * 1024) return false;
+  if (!attn_valu_supported(L, DH)) return false;
   const int rows = attn_rows(L);
   const dim3 grid((unsigned)KBH, cdiv(L, rows));
   const size_t sh = (size_t)2 * L * DH * sizeof(float);
@@ -312,7 +317,7 @@ bool attn_bwd(const void* dout, const void* q, const void* k, const void* v, con
     return attn_bwd_mfma(dout, q, k, v, o, lse, key_valid, dq, dk, dv, delta, KBH, H, L, DH, f32, s, ldqkv, ldo,
                          drop_seeds, heads_per_client, drop_p);
   if (ldqkv || ldo || drop_p > 0.f) return false;
-  if (!attn_supported(L, DH) || (2L * L * DH + 2L * L) * 4 > 160L * 1024) return false;
+  if (!attn_valu_supported(L, DH)) return false;
   const int rows = attn_rows(L);
   const dim3 grid((unsigned)KBH, cdiv(L, rows));
   const float scale = 1.0f / sqrtf((float)DH);

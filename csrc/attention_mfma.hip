@@ -24,7 +24,9 @@
 // Dropout (p > 0): P̃ = P∘M/(1−p) with M the keep mask hash(head, query, key) of the client's
 // seed — the same mask in all three kernels and in ops/ref.py. The forward normalises with the
 // undropped P (l, lse) and accumulates O = P̃V; the backward uses dP = (dO·Vᵀ)∘M/(1−p) in
-// dS = P∘(dP − δ) with δ = rowsum(dO∘O), and dV = P̃ᵀdO.
+// dS = P∘(dP − δ) with δ = rowsum(dO∘O), and dV = P̃ᵀdO. The MFMA operand is P∘M; the factor
+// 1/(1−p) multiplies O, dV and dP in fp32 outside the products (one multiply per output element
+// instead of one per score, and P is split as it is without dropout).
 #include "common.h"
 #include "dls.h"
 #include "gemm_common.h"
@@ -245,7 +247,12 @@ __device__ __forceinline__ float attn_keep(const AttnDropArgs& d, long head, int
   const uint32_t seed = d.seeds[head / d.hpc];
   const uint32_t idx = (uint32_t)(((long)(head % d.hpc) * L + qi) * L + kj);
   const uint32_t thr = (uint32_t)fminf(d.p * 4294967296.f, 4294967040.f);
-  return mix32(idx, seed) >= thr ? 1.f / (1.f - d.p) : 0.f;
+  return mix32(idx, seed) >= thr ? 1.f : 0.f;
+}
+// the factor 1/(1−p) of the kept probabilities: applied to O, dV and dP outside the MFMA products
+// (as fp32 multiplies), so P keeps the operand split it has without dropout
+__device__ __forceinline__ float attn_drop_rescale(const AttnDropArgs& d, bool drop) {
+  return drop ? 1.f / (1.f - d.p) : 1.f;
 }
 
 __device__ __forceinline__ int crow(int e) { return (e & 3) + 8 * (e >> 2) + 4 * ((threadIdx.x & 63) >> 5); }
@@ -323,7 +330,7 @@ __global__ void __launch_bounds__(WG, (sizeof(T) == 4 && DH == 48) ? 3 : 4) attn
     __syncthreads();  // K / V / P tiles are rewritten next block
   }
   if (qok) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    const float inv = (l > 0.f ? 1.f / l : 0.f) * attn_drop_rescale(dr, drop);
 #pragma unroll
     for (int t = 0; t < DP / 32; ++t)
       store_rowcols<T, DH>(o + obase + (long)qrow * lo.ld, t * 32, ot[t], inv);
@@ -360,21 +367,41 @@ __global__ void __launch_bounds__(WG, 3) attn_bwd_dq_mfma_kernel(const T* __rest
     qf[ks] = frag_global<T>(q + base + (long)qrow * lq.ld + d, n);
     df[ks] = frag_global<T>(dout + obase + (long)qrow * lo.ld + d, n);
   }
-  // δ = dO·O of this lane's query (the two half-waves take alternate 4-column chunks)
+  // δ = dO·O of this lane's query (the two half-waves take alternate 4-column chunks).
+  // fp32: dS = P∘(dP − δ) subtracts δ from dP = dO·Vᵀ, which the MFMAs form from operands split
+  // hi + lo with the lo·lo term dropped, then times 1/(1−p). δ is formed the same way from dO and
+  // O·(1−p) (the forward's unscaled P·V). Where a query's probability sits on one key — a sequence
+  // with one valid key — O·(1−p) is that key's v as the forward split it and dP = δ: formed alike
+  // the two cancel to fp32 rounding, where an fp32 dot dO·O left 2⁻¹⁸ of |dO||v| per column, which
+  // dK of that key then summed over every query (1.6e-4 to 2.3e-4 at L = 129, where dK is 0).
+  const float rf = attn_drop_rescale(dr, drop);
   float dl = 0.f;
   if (qok) {
     const T* dr_ = dout + obase + (long)qrow * lo.ld;
     const T* orow = o + obase + (long)qrow * lo.ld;
+    const float unscale = drop ? 1.f - dr.p : 1.f;
 #pragma unroll
     for (int d = 4 * h; d < DH; d += 8) {
       float a[4], b[4];
       load_vec<4>(dr_ + d, a);
       load_vec<4>(orow + d, b);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dl = fmaf(a[i], b[i], dl);
+      for (int i = 0; i < 4; ++i) {
+        if constexpr (sizeof(T) == 4) {
+          bf16_t ah, al, bh, bl;
+          split2(a[i], ah, al);
+          split2(b[i] * unscale, bh, bl);
+          dl = fmaf(bf2f(al), bf2f(bh), dl);
+          dl = fmaf(bf2f(ah), bf2f(bl), dl);
+          dl = fmaf(bf2f(ah), bf2f(bh), dl);
+        } else {
+          dl = fmaf(a[i], b[i], dl);
+        }
+      }
     }
   }
   dl += __shfl_xor(dl, 32, 64);
+  if constexpr (sizeof(T) == 4) dl *= rf;
   if (qok && h == 0) delta[head * L + qrow] = dl;
   const float lse_q = qok ? lse[head * L + qrow] : 0.f;
   f32x16 dqt[DP / 32];
@@ -397,7 +424,7 @@ __global__ void __launch_bounds__(WG, 3) attn_bwd_dq_mfma_kernel(const T* __rest
     for (int e = 0; e < 16; ++e) {
       const bool ok = qok && (k0 + crow(e) < nk);
       const float p = ok ? __expf(st[e] * scale - lse_q) : 0.f;
-      const float dp = (drop && p != 0.f) ? dpt[e] * attn_keep(dr, head, L, qrow, k0 + crow(e)) : dpt[e];
+      const float dp = (drop && p != 0.f) ? dpt[e] * attn_keep(dr, head, L, qrow, k0 + crow(e)) * rf : dpt[e];
       st[e] = p * (dp - dl) * scale;  // dSᵀ
     }
     put_colrows<T>(PI, st);  // dS[query][key]
@@ -444,6 +471,7 @@ __global__ void __launch_bounds__(WG, 2) attn_bwd_dkv_mfma_kernel(const T* __res
   const int key = blockIdx.y * (4 * RB) + wid * RB + c;
   const bool kok = key < nk;
   const bool drop = dr.seeds != nullptr && dr.p > 0.f;
+  const float rf = attn_drop_rescale(dr, drop);
   const Img<T> QI{Qs, LDK, RB * LDK}, OI{Os, LDK, RB * LDK};
   const Img<T> PI{Ps[wid], LDP, RB * LDP}, SI{Ss[wid], LDP, RB * LDP};
 
@@ -491,8 +519,8 @@ __global__ void __launch_bounds__(WG, 2) attn_bwd_dkv_mfma_kernel(const T* __res
       const bool ok = kok && (q0 + qr < L);
       const float p = ok ? __expf(s[e] * scale - Lq[qr]) : 0.f;
       const float mk = (drop && p != 0.f) ? attn_keep(dr, head, L, q0 + qr, key) : 1.f;
-      s[e] = p * mk;                              // P̃ (dV)
-      dp[e] = p * (dp[e] * mk - Dq[qr]) * scale;  // dS = P∘(dP − δ), in place
+      s[e] = p * mk;                                   // P∘M (dV; its 1/(1−p) at the store)
+      dp[e] = p * (dp[e] * mk * rf - Dq[qr]) * scale;  // dS = P∘(dP − δ), in place
     }
     put_colrows<T>(PI, s);   // P̃[key][query]
     put_colrows<T>(SI, dp);  // dS[key][query]
@@ -510,7 +538,7 @@ __global__ void __launch_bounds__(WG, 2) attn_bwd_dkv_mfma_kernel(const T* __res
 #pragma unroll
     for (int t = 0; t < DP / 32; ++t) {
       store_rowcols<T, DH>(dk + base + (long)key * lq.ld, t * 32, dkt[t], 1.f);
-      store_rowcols<T, DH>(dv + base + (long)key * lq.ld, t * 32, dvt[t], 1.f);
+      store_rowcols<T, DH>(dv + base + (long)key * lq.ld, t * 32, dvt[t], rf);
     }
   }
 }

@@ -687,7 +687,10 @@ long embedding_bwd_part_floats(long n, int D);
 void seq_mean_fwd(const void* x, const int* len, void* y, long S, int L, int D, int f32, hipStream_t s);
 void seq_mean_bwd(const void* dy, const int* len, void* dx, long S, int L, int D, int f32, hipStream_t s);
 // --------------------------------------------------------------- attention / graph
+// attn_supported: attn_fwd / attn_bwd have a kernel for (L, DH) under the current attn_mfma option
+// (the MFMA kernels when in use, else the VALU kernels: attn_valu_supported)
 bool attn_supported(int L, int DH);
+bool attn_valu_supported(int L, int DH);
 // MFMA flash attention (attention_mfma.hip), head dim 32 / 64; attn_fwd / attn_bwd route to it
 bool attn_mfma_supported(int L, int DH);
 // ldqkv / ldo > 0: q/k/v (and dq/dk/dv) are column blocks of packed [KB][L][ldqkv] rows, o / do

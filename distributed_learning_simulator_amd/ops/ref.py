@@ -354,14 +354,21 @@ def attn_drop_scale(shape, seeds, p: float, device) -> torch.Tensor:
 def attn_fwd(q, k, v, key_valid=None, drop_p: float = 0.0, drop_seeds=None):
     """q,k,v [K,B,Hh,L,dh]; key_valid [K,B] number of valid keys (padding mask) or None;
     drop_p / drop_seeds [K]: dropout on the attention probabilities (nn.MultiheadAttention's
-    `dropout`). Returns o and the log-sum-exp [K,B,Hh,L] (fp32, of the undropped scores)."""
+    `dropout`). Returns o and the log-sum-exp [K,B,Hh,L] (fp32, of the undropped scores).
+    A sequence without a valid key (key_valid = 0: an empty text) gives o = 0 and lse = 0, as the
+    kernels do (csrc/attention*.hip `l > 0 ? … : 0`); with that lse `attn_bwd` gives it p = 0 and
+    zero gradients."""
     scale = q.shape[-1] ** -0.5
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+    empty = None
     if key_valid is not None:
         L = k.shape[-2]
         km = torch.arange(L, device=q.device)[None, None, :] < key_valid[..., None].to(q.device)
         s = s.masked_fill(~km[:, :, None, None, :], float("-inf"))
+        empty = (key_valid.to(q.device) <= 0)[:, :, None, None]
     lse = torch.logsumexp(s, dim=-1)
+    if empty is not None:
+        lse = lse.masked_fill(empty, 0.0)  # (−inf there: exp(s − lse) would be NaN, now exp(−inf) = 0)
     p = torch.exp(s - lse[..., None])
     if drop_p:
         p = p * attn_drop_scale(q.shape, drop_seeds, drop_p, q.device)

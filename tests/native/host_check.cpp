@@ -73,13 +73,26 @@ int main() {
           (void)conv_gl_wanted(K, M, co, ci, 9, -1);
           (void)conv_gl_supported(ci, co, 9);
         }
-  // 3) attention support predicates
-  for (int L = 1; L <= 1024; L += 37)
-    for (int dh : {8, 16, 20, 32, 50, 64, 100, 128}) {
-      const bool packed = attn_packed_supported(L, dh), mfma = attn_mfma_supported(L, dh);
-      (void)attn_supported(L, dh);
-      CHECK(!packed || mfma || attn_supported(L, dh), "packed without a kernel L=%d dh=%d", L, dh);
-    }
+  // 3) attention support predicates, under both settings of the attn_mfma option: attn_supported is
+  //    "the MFMA kernels are in use, or the VALU kernels fit" (what attn_fwd / attn_bwd launch), and
+  //    the packed layouts exist on the MFMA kernels only. The VALU bound is restated here: head dims
+  //    8 / 16 / 20 / 32 / 64 and the dK/dV kernel's (2·L·dh + 2·L) fp32 within 160 KiB of LDS.
+  for (int opt = 0; opt < 2; ++opt) {
+    CHECK(set_native_option("attn_mfma", opt), "attn_mfma option");
+    for (int L = 1; L <= 1024; L += 37)
+      for (int dh : {8, 16, 20, 32, 48, 50, 64, 100, 128}) {
+        const bool packed = attn_packed_supported(L, dh), mfma = opt != 0 && attn_mfma_supported(L, dh);
+        const bool valu_dh = dh == 8 || dh == 16 || dh == 20 || dh == 32 || dh == 64;
+        const bool valu = valu_dh && (2L * L * dh + 2L * L) * 4 <= 160L * 1024;
+        CHECK(attn_valu_supported(L, dh) == valu, "VALU predicate L=%d dh=%d", L, dh);
+        CHECK(attn_supported(L, dh) == (mfma || valu), "attn_supported L=%d dh=%d attn_mfma=%d", L, dh, opt);
+        CHECK(packed == mfma, "packed without the MFMA kernels L=%d dh=%d attn_mfma=%d", L, dh, opt);
+        CHECK(!packed || attn_supported(L, dh), "packed without a kernel L=%d dh=%d", L, dh);
+      }
+  }
+  CHECK(attn_mfma_supported(37, 48) && !attn_valu_supported(37, 48), "dh 48 is an MFMA-only head dim");
+  CHECK(attn_valu_supported(300, 64) && !attn_valu_supported(700, 64), "VALU LDS bound at dh 64");
+  set_native_option("attn_mfma", kOptUnset);
   printf("host_check: %ld fast-division cases, %d failures\n", checked, failures);
   return failures ? 1 : 0;
 }

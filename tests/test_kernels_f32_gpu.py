@@ -279,7 +279,8 @@ def test_dense_block_strided_kernels_match_cpu(hip, dtype, tol):
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 3e-5), (torch.bfloat16, 2.5e-2)])
 def test_attention_mfma(hip, L, dh, dtype, tol):
     """MFMA flash attention (csrc/attention_mfma.hip): ragged key padding, partial 128-row blocks,
-    bf16 and split-bf16 fp32, against the float64 oracle."""
+    bf16 and split-bf16 fp32, against fp32 `ops.ref` on the upcast inputs (`ref.attn_fwd` / `attn_bwd`
+    cast their arguments to fp32; the float64 oracle is in tests/test_attention_edges_gpu.py)."""
     K, B, H = 2, 2, 2
     torch.manual_seed(L + dh)
     q, k, v = (_f(K, B, H, L, dh).to(dtype) for _ in range(3))
@@ -306,7 +307,7 @@ def test_attention_mfma(hip, L, dh, dtype, tol):
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 3e-5), (torch.bfloat16, 2.5e-2)])
 def test_attention_packed_qkv(hip, L, H, D, dtype, tol):
     """Attention read straight from the QKV projection rows [K, B, L, 3D] (strided heads, no
-    permute copies) and the gradient written back in that layout: against the float64 oracle
+    permute copies) and the gradient written back in that layout: against fp32 `ops.ref`
     applied to the explicitly split / permuted q, k, v."""
     K, B = 2, 2
     dh = D // H
@@ -599,7 +600,7 @@ def test_conv_halo(hip, case):
 def test_attention_padded_heads_and_dropout(hip, L, H, D, drop_p, dtype, tol):
     """MFMA flash attention at the reference imdb model's dh = 20 (d_model 100, 5 heads: padded
     to 32 on the MFMA, packed QKV rows read in place) and with attention-probability dropout
-    (nn.MultiheadAttention's dropout): against the float64 oracle with the same hash mask."""
+    (nn.MultiheadAttention's dropout): against fp32 `ops.ref` with the same hash mask."""
     K, B = 2, 3
     dh = D // H
     assert hip.attn_packed_supported(L, dh)
