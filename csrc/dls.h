@@ -526,6 +526,22 @@ void topk_decode(const int* idx, const float* val, float* out, long ld, int K, l
 void topk_accumulate(const int* idx, const float* val, const double* w, double* acc, int K, long P, int k,
                      hipStream_t s);
 
+// ---- 1-bit rotated payloads (csrc/rotsign.hip, ops/compress.py RotSignPayload)
+// Per row k and block of ROTSIGN_BLOCK flat elements (nb = ceil(P / ROTSIGN_BLOCK)): sign bits of the
+// randomised Hadamard rotation of the block, bits [K][nb · 512] LSB-first, and its fp32 scale [K][nb]
+// (mse: L1 / 4096, else L2 / L1). seeds [K] key the ±1 diagonal; vbits as for top-k. err != nullptr: the
+// error-feedback form (always mse): u = delta + err is packed and err ← u − decode (0 at padding).
+// Rows 16-B aligned, P % 16 == 0.
+#define ROTSIGN_BLOCK 4096
+void rotsign_pack(const float* delta, long ld_d, float* err, long ld_e, const uint32_t* vbits, const uint32_t* seeds,
+                  uint8_t* bits, float* scale, int K, long P, int mse, hipStream_t s);
+// out [K][P] (row stride ld) = the decoded rows, 0.0 at padding
+void rotsign_unpack(const uint8_t* bits, const float* scale, const uint32_t* vbits, const uint32_t* seeds, float* out,
+                    long ld, int K, long P, hipStream_t s);
+// acc [P] fp64: acc[i] = acc[i] + w[k] · decode_k[i] for k ascending (padding untouched; bitwise reproducible)
+void rotsign_accumulate(const uint8_t* bits, const float* scale, const uint32_t* vbits, const uint32_t* seeds,
+                        const double* w, double* acc, int K, long P, hipStream_t s);
+
 // ---- robust aggregation (csrc/robust.hip, ops/ref.py trimmed_sum)
 // out[c] (fp64, c < P) = the n values of column c of x [n][P] (row stride ld, rows 16-B aligned,
 // P % 4 == 0) sorted by the signed key bits ^ ((bits >> 31) & 0x7fffffff), the b lowest and b highest

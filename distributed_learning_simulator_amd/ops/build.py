@@ -44,7 +44,10 @@ FILE_FLAGS = {"compress.hip": ["-ffp-contract=on"],
               "dp.hip": ["-ffp-contract=off"],
               # server_opt.hip: β·m, c·d, c·q, lr·m' and the sums that follow them are rounded separately
               # (the contract of ops/ref.py server_opt_step, where each is its own statement)
-              "server_opt.hip": ["-ffp-contract=off"]}
+              "server_opt.hip": ["-ffp-contract=off"],
+              # rotsign.hip: w·x̂ and the fp64 add that follows are rounded separately (the accumulate contract
+              # of ops/compress.py RotSignPayload); the butterflies themselves are single adds
+              "rotsign.hip": ["-ffp-contract=off"]}
 # (secagg.hip needs no entry: integer arithmetic in Z_{2^32}, and its one fp64 product, t · 2^f, is exact)
 
 

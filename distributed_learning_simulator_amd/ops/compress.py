@@ -26,6 +26,10 @@ Codes:
 
 x̂ = lo + q·scale; the CPU path below writes the identical buffer and decodes to identical bits.
 
+`RotSignPayload` (fed_drive, csrc/rotsign.hip) is the 1-bit member (DRIVE / EDEN): per client and per
+block of 4096 flat elements the sign bits of a randomised Hadamard rotation and one fp32 scale, 516
+bytes per block, with the same decode / accumulate interface; `pack_rotsign_ef` keeps the residual.
+
 `MaskedPayload` (fed_secagg, csrc/secagg.hip) carries the masked fixed-point rows of secure aggregation:
 int32 words that only add up (`accumulate` into an int64 ring accumulator); there is no dense form to decode.
 """
@@ -37,7 +41,7 @@ from dataclasses import dataclass
 import torch
 
 from . import backend, ref
-from .fl import uniform_rows
+from .fl import _mix, uniform_rows
 
 
 @dataclass
@@ -357,6 +361,182 @@ def pack_topk_ef(delta: torch.Tensor, err: torch.Tensor, meta: LayoutMeta, k: in
 
     idx, val = hip.topk_pack(delta, err, meta, k)
     return SparsePayload(idx, val, meta, k)
+
+
+# ------------------------------------------------------------------ 1-bit rotated payloads (DRIVE / EDEN)
+ROT_BLOCK = 4096  # 4⁶: the normalisation 1/√B = 2⁻⁶ is an exact scaling
+
+
+@dataclass
+class RotSignPayload:
+    """1-bit upload of K clients (fed_drive, csrc/rotsign.hip): per row and per block of 4096 flat
+    elements the sign bits of its randomised Hadamard rotation and one fp32 scale. Contract (CPU
+    oracle below ≡ the kernels), block b = flat indices [4096 b, 4096 (b + 1)):
+    - u_i reads as +0.0 at i ≥ P and at inter-tensor padding; z_i = u_i · d_i with d_i = −1 iff bit 31
+      of mix32(i, seed_k) is set (`fl.uniform_rows`' hash of the flat index);
+    - fp32 FWHT: stages h = 1, 2, …, 2048 in that order, (a, b) → (a + b, a − b) for the pairs
+      (j, j + h) with j & h = 0, one rounding each; y = z′ · 2⁻⁶;
+    - L1 = Σ|y_j|, L2 = Σ y_j² in fp64, each added as an adjacent-pair tree over j;
+    - scale S = fp32(L2 / L1) ("unbiased", DRIVE: ⟨x̂, u⟩ = ‖u‖²) or fp32(L1 / 4096) ("mse": the
+      projection onto the sign pattern, for error feedback); L1 = 0 gives S = 0;
+    - bit j = sign bit of y_j, LSB-first (byte j >> 3, bit j & 7);
+    - decode: t_j = ±S from the bits, the same FWHT, · 2⁻⁶, · d_i; 0.0 at padding.
+    A non-finite element makes its block's scale, and so its decoded block, non-finite."""
+
+    bits: torch.Tensor  # uint8 [K, nb · 512]
+    scale: torch.Tensor  # fp32 [K, nb]
+    seeds: list
+    meta: LayoutMeta
+    _seeds_dev: torch.Tensor | None = None
+
+    @property
+    def K(self) -> int:
+        return self.bits.shape[0]
+
+    @property
+    def nb(self) -> int:
+        return self.scale.shape[1]
+
+    def row_bytes(self) -> list[int]:
+        """Per client: its code bytes + its fp32 block scales (516 per block)."""
+        per = self.bits[0].numel() * self.bits.element_size() + self.scale[0].numel() * self.scale.element_size()
+        return [per] * self.K
+
+    def seeds_dev(self) -> torch.Tensor:
+        """int32 [K] on the payload's device (the kernels' copy of `seeds`)."""
+        if self._seeds_dev is None:
+            self._seeds_dev = _rot_seeds(self.seeds, self.bits.device)
+        return self._seeds_dev
+
+    def decode(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        K, P = self.K, self.meta.P
+        if out is None:
+            out = torch.empty((K, P), dtype=torch.float32, device=self.bits.device)
+        assert out.shape == (K, P) and out.dtype == torch.float32 and out.stride(1) == 1
+        if backend.get(out) is ref:
+            out.copy_(_rot_decode_torch(self))
+            return out
+        from . import hip
+
+        hip.rotsign_unpack(self, out)
+        return out
+
+    def accumulate(self, acc: torch.Tensor, w: torch.Tensor) -> None:
+        """acc [P] fp64: acc[i] = acc[i] + (w[k] · x̂_k[i]) for k ascending, product and sum rounded
+        separately; padding is not touched."""
+        assert acc.dtype == torch.float64 and acc.shape == (self.meta.P,)
+        w = w.to(acc.device, torch.float64).contiguous()
+        assert w.numel() == self.K
+        if backend.get(acc) is ref:
+            valid = self.meta.seg_ids < self.meta.nseg
+            x = _rot_decode_torch(self).double()[:, valid]
+            a = acc[valid]
+            for k in range(self.K):
+                a = a + w[k] * x[k]
+            acc[valid] = a
+            return
+        from . import hip
+
+        hip.rotsign_accumulate(self, w, acc)
+
+
+def _rot_seeds(seeds, device) -> torch.Tensor:
+    return torch.tensor([s & 0xFFFFFFFF for s in seeds], dtype=torch.int64).to(torch.int32).to(device)
+
+
+def _rot_diag(seeds, n: int, device) -> torch.Tensor:
+    """[K, n] fp32 ±1: −1 where bit 31 of the hash of (flat index, row seed) is set."""
+    idx = torch.arange(n, device=device, dtype=torch.int64)
+    return torch.stack([1.0 - 2.0 * (_mix(idx, s & 0xFFFFFFFF) >> 31).float() for s in seeds])
+
+
+def _rot_fwht(z: torch.Tensor) -> torch.Tensor:
+    """The contract's transform of every length-4096 vector along the last axis (fp32)."""
+    shape = z.shape
+    h = 1
+    while h < ROT_BLOCK:
+        z = z.reshape(-1, ROT_BLOCK // (2 * h), 2, h)
+        a, b = z[:, :, 0, :], z[:, :, 1, :]
+        z = torch.stack((a + b, a - b), dim=2)
+        h *= 2
+    return z.reshape(shape) * 2.0 ** -6
+
+
+def _rot_tree(v: torch.Tensor) -> torch.Tensor:
+    while v.shape[-1] > 1:
+        v = v[..., 0::2] + v[..., 1::2]
+    return v[..., 0]
+
+
+def _rot_blocks(u: torch.Tensor, meta: LayoutMeta) -> torch.Tensor:
+    """[K, nb · 4096]: the rows with +0.0 at padding and beyond P."""
+    K, P = u.shape
+    nb = -(-P // ROT_BLOCK)
+    z = torch.zeros((K, nb * ROT_BLOCK), dtype=torch.float32, device=u.device)
+    z[:, :P] = torch.where((meta.seg_ids < meta.nseg)[None, :], u, torch.zeros((), device=u.device))
+    return z
+
+
+def _rot_pack_torch(u: torch.Tensor, meta: LayoutMeta, seeds, mse: bool) -> RotSignPayload:
+    K = u.shape[0]
+    z = _rot_blocks(u, meta)
+    nb = z.shape[1] // ROT_BLOCK
+    y = _rot_fwht((z * _rot_diag(seeds, z.shape[1], u.device)).view(K, nb, ROT_BLOCK))
+    yd = y.double()
+    L1, L2 = _rot_tree(yd.abs()), _rot_tree(yd * yd)
+    if mse:
+        S = (L1 / ROT_BLOCK).float()
+    else:
+        S = torch.where(L1 == 0, torch.zeros_like(L1), L2 / L1).float()
+    neg = (y.contiguous().view(torch.int32) < 0).view(K, nb * ROT_BLOCK // 8, 8).long()
+    bits = (neg << torch.arange(8, device=u.device)).sum(2).to(torch.uint8)
+    return RotSignPayload(bits.contiguous(), S.contiguous(), list(seeds), meta)
+
+
+def _rot_decode_torch(p: RotSignPayload) -> torch.Tensor:
+    K, nb, P = p.K, p.nb, p.meta.P
+    dev = p.bits.device
+    neg = ((p.bits.long()[:, :, None] >> torch.arange(8, device=dev)) & 1).bool().view(K, nb, ROT_BLOCK)
+    S = p.scale[:, :, None]
+    x = _rot_fwht(torch.where(neg, -S, S)).view(K, nb * ROT_BLOCK) * _rot_diag(p.seeds, nb * ROT_BLOCK, dev)
+    return torch.where((p.meta.seg_ids < p.meta.nseg)[None, :], x[:, :P], torch.zeros((), device=dev))
+
+
+def _check_rot(u: torch.Tensor, meta: LayoutMeta, seeds) -> None:
+    assert u.dim() == 2 and u.shape[1] == meta.P and u.dtype == torch.float32 and u.stride(1) == 1
+    assert meta.P < 2 ** 31, "the diagonal hashes a 32-bit flat index"
+    assert len(seeds) == u.shape[0], "one seed per client row"
+
+
+def pack_rotsign(u: torch.Tensor, meta: LayoutMeta, seeds: list[int], scale: str = "unbiased") -> RotSignPayload:
+    """1-bit rotated payload of rows u [K, P] (u is not modified). scale: "unbiased" | "mse"."""
+    assert scale in ("unbiased", "mse"), scale
+    _check_rot(u, meta, seeds)
+    if backend.get(u) is ref:
+        return _rot_pack_torch(u, meta, seeds, scale == "mse")
+    from . import hip
+
+    sd = _rot_seeds(seeds, u.device)
+    bits, S = hip.rotsign_pack(u, None, meta, sd, scale == "mse")
+    return RotSignPayload(bits, S, list(seeds), meta, sd)
+
+
+def pack_rotsign_ef(delta: torch.Tensor, err: torch.Tensor, meta: LayoutMeta, seeds: list[int]) -> RotSignPayload:
+    """Error-feedback form ("mse" scale): packs u = delta + err and leaves err ← u − x̂ in place (0 at
+    padding). delta [K, P] is only read; err [K, P] are the residual rows."""
+    _check_rot(delta, meta, seeds)
+    _check_rot(err, meta, seeds)
+    assert err.shape == delta.shape and err.data_ptr() != delta.data_ptr()
+    if backend.get(delta) is ref:
+        u = delta + err
+        p = _rot_pack_torch(u, meta, seeds, True)
+        err.copy_(torch.where((meta.seg_ids < meta.nseg)[None, :], u - _rot_decode_torch(p), torch.zeros(())))
+        return p
+    from . import hip
+
+    sd = _rot_seeds(seeds, delta.device)
+    bits, S = hip.rotsign_pack(delta, err, meta, sd, True)
+    return RotSignPayload(bits, S, list(seeds), meta, sd)
 
 
 # ------------------------------------------------------------------ masked uploads (secure aggregation)

@@ -1511,6 +1511,40 @@ def topk_accumulate(p, w, acc):
     _C.topk_accumulate(_p(p.idx), _p(p.val), _p(w), _p(acc), p.K, p.meta.P, p.k, _s())
 
 
+def rotsign_pack(delta, err, meta, seeds_dev, mse: bool):
+    """csrc/rotsign.hip: (bits uint8 [K, nb·512], scale fp32 [K, nb]) of the rotated rows. err None:
+    delta is packed as is. Else u = delta + err is packed ("mse" scale) and err ← u − x̂."""
+    K, P = delta.shape
+    assert P == meta.P and P % 16 == 0 and seeds_dev.numel() == K and seeds_dev.dtype == torch.int32
+    _rows16(delta, "delta")
+    if err is not None:
+        _rows16(err, "err")
+        assert err.shape == delta.shape
+    nb = -(-P // _C.rotsign_block())
+    bits = torch.empty((K, nb * 512), dtype=torch.uint8, device=delta.device)
+    scale = torch.empty((K, nb), dtype=torch.float32, device=delta.device)
+    _C.rotsign_pack(_p(delta), delta.stride(0), _p(err), err.stride(0) if err is not None else 0,
+                    _p(meta.valid_bits()), _p(seeds_dev), _p(bits), _p(scale), K, P, int(mse), _s())
+    return bits, scale
+
+
+def _rotsign_args(p):
+    _check(p.bits, torch.uint8, name="bits")
+    _check(p.scale, F32, name="scale")
+    assert p.bits.shape == (p.K, p.nb * 512) and p.nb == -(-p.meta.P // _C.rotsign_block()) and p.meta.P % 16 == 0
+    return _p(p.bits), _p(p.scale), _p(p.meta.valid_bits()), _p(p.seeds_dev())
+
+
+def rotsign_unpack(p, out):
+    _rows16(out, "out")
+    _C.rotsign_unpack(*_rotsign_args(p), _p(out), out.stride(0), p.K, p.meta.P, _s())
+
+
+def rotsign_accumulate(p, w, acc):
+    assert w.dtype == torch.float64 and w.numel() == p.K and w.is_cuda and acc.is_contiguous() and acc.is_cuda
+    _C.rotsign_accumulate(*_rotsign_args(p), _p(w), _p(acc), p.K, p.meta.P, _s())
+
+
 # ---------------------------------------------------------------------- GNN sampling
 def _hmix_int(h: int) -> int:
     h &= 0x7FFFFFFF

@@ -11,7 +11,8 @@ one rank). `TopKErrorFeedbackWorker` is a concrete sparsifier (largest-|x| fract
 client row; wire bytes = k values + k int32 indices). `PackedTopKWorker` (method `fed_topk`) is
 the full form: an exact, tie-ordered selection by the hand-written kernels of csrc/topk.hip into
 a packed `ops.compress.SparsePayload` that the server accumulates directly; no dense sparse
-rows exist on the client side.
+rows exist on the client side. `RotSignWorker` (method `fed_drive`) uploads one sign bit per
+coordinate of a randomised Hadamard rotation (csrc/rotsign.hip), with or without the residual.
 """
 
 from __future__ import annotations
@@ -19,7 +20,7 @@ from __future__ import annotations
 import torch
 
 from ..message import CohortMessage
-from ..ops import compress
+from ..ops import compress, fl
 from .aggregation_worker import AggregationWorker
 
 
@@ -109,6 +110,46 @@ class PackedTopKWorker(ErrorFeedbackWorker):
             error[idx] = err
         # the upload is the packed payload (topology/endpoints._attach); the dense rows stay only
         # as the receiver's decode target
+        msg.payload = payload
+        msg.extra["decode_into"] = rows
+        msg.data = None
+        msg.extra["wire_bytes"] = payload.row_bytes()
+        return msg
+
+
+class RotSignWorker(ErrorFeedbackWorker):
+    """1-bit rotated uploads (method `fed_drive`, csrc/rotsign.hip): every client sends the sign bits
+    of the randomised Hadamard rotation of its delta and one fp32 scale per 4096-element block
+    (`ops.compress.RotSignPayload`). `algorithm_kwargs.error_feedback`:
+    - false (default): DRIVE's unbiased scale, no client state, so partial participation works;
+    - true: the MSE-optimal scale with the residual e ← (Δ + e) − x̂ kept in `_error`, which needs
+      the stable client→rank assignment of every error-feedback worker.
+    The rotation's diagonal is keyed by (round's upload seed, client id): it changes every round and
+    does not depend on which rank or row hosts a client."""
+
+    def __init__(self, config, endpoint, session=None, **kwargs):
+        super().__init__(config, endpoint, session, **kwargs)
+        self.error_feedback = bool(config.algorithm_kwargs.get("error_feedback", False))
+        self._meta: compress.LayoutMeta | None = None
+
+    def _get_sent_data(self, wave, theta_g, stats) -> CohortMessage:
+        msg = AggregationWorker._get_sent_data(self, wave, theta_g, stats)
+        rows = msg.data
+        K, P = rows.shape
+        if self._meta is None or self._meta.seg_ids.device != rows.device:
+            self._meta = compress.LayoutMeta.of(self.trainer.layout, rows.device)
+        seeds = fl.row_seeds(self.upload_seed(self._round_num), list(wave))
+        if not self.error_feedback:
+            payload = compress.pack_rotsign(rows, self._meta, seeds, scale="unbiased")
+        else:
+            error = self._ensure_error(P, rows.device)
+            if list(wave) == list(range(wave[0], wave[0] + K)):
+                payload = compress.pack_rotsign_ef(rows, error[wave[0] : wave[0] + K], self._meta, seeds)
+            else:
+                idx = torch.tensor(wave, device=rows.device)
+                err = error[idx]
+                payload = compress.pack_rotsign_ef(rows, err, self._meta, seeds)
+                error[idx] = err
         msg.payload = payload
         msg.extra["decode_into"] = rows
         msg.data = None

@@ -23,6 +23,10 @@ $S --config-name fed_paq/cifar100.yaml ++fed_paq.round=1 ++fed_paq.epoch=1 ++fed
    ++fed_paq.algorithm_kwargs.random_client_number=2
 # top-k sparsified uploads with error feedback (packed payload)
 $S --config-name fed_topk/mnist.yaml ++fed_topk.round=1 ++fed_topk.epoch=1 ++fed_topk.worker_number=2
+# 1-bit rotated uploads (DRIVE: Hadamard rotation + sign bits): unbiased, then with error feedback
+$S --config-name fed_drive/mnist.yaml ++fed_drive.round=1 ++fed_drive.epoch=1 ++fed_drive.worker_number=2
+$S --config-name fed_drive/mnist.yaml ++fed_drive.round=2 ++fed_drive.epoch=1 ++fed_drive.worker_number=2 \
+   ++fed_drive.algorithm_kwargs.error_feedback=true
 # robust aggregation (coordinate-wise trimmed mean / median) with Byzantine clients
 $S --config-name fed_trimmed_mean/mnist.yaml ++fed_trimmed_mean.round=1 ++fed_trimmed_mean.epoch=1 ++fed_trimmed_mean.worker_number=5 \
    ++fed_trimmed_mean.algorithm_kwargs.byzantine_number=1 ++fed_trimmed_mean.debug=True
