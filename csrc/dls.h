@@ -479,6 +479,19 @@ void ln_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
             hipStream_t s);
 long col_sum_workspace_floats(int K, long rows, int C);
 long ln_workspace_floats(int K, long rows_per_client, int C);
+// GroupNorm (csrc/groupnorm.hip) of [K][B][HW][C] activations: G groups of C / G adjacent channels,
+// mean / rstd [K][B][G], one workgroup per sample. valid [K]: samples b >= valid[k] are not read,
+// their outputs are +0. yp (fp32): y's split planes [K][2][B][HW][C] as well. gn_bwd: the gate is
+// y > 0 (relu), dres (optional) = the gated dy; ws (gn_workspace_floats): per-sample dγ / dβ rows,
+// folded over b < valid[k] ascending into dgamma / dbeta (row stride dg_cs) — no atomics.
+bool gn_shape_ok(int HW, int C, int G);
+long gn_workspace_floats(int K, int B, int C);
+void gn_fwd(const void* x, const void* res, const void* gamma, const void* beta, void* y, bf16_t* yp, float* mean,
+            float* rstd, const int* valid, long g_cs, int rep, int K, int B, int HW, int C, int G, float eps, int relu,
+            int f32, hipStream_t s);
+void gn_bwd(const void* dy, const void* x, const void* y, const float* mean, const float* rstd, const void* gamma,
+            const int* valid, long g_cs, int rep, int K, int B, int HW, int C, int G, int relu, void* dx, void* dres,
+            float* dgamma, float* dbeta, long dg_cs, float* ws, int f32, hipStream_t s);
 void col_sum(const void* x, float* out, long out_cs, int K, long rows, int C, int f32, hipStream_t s,
              float* ws = nullptr);
 

@@ -173,9 +173,43 @@ class BatchNorm(Module):
                              stats=stats, planes=planes)
 
 
-def conv_bn(conv: Conv2d, bn: BatchNorm, x, ctx, conv_link=None, conv_donor=None, **bn_kw):
+class GroupNorm(Module):
+    """GroupNorm (Wu & He 2018) over `groups` groups of adjacent channels: one statistic per
+    (client, sample, group), so a sample's output does not depend on the rest of its batch — the
+    normalisation federated ResNets use on non-IID shards. Optional fused residual-add + ReLU."""
+
+    kind = "GroupNorm"
+
+    def __init__(self, c, groups, relu=False):
+        super().__init__()
+        if groups < 1 or c % groups:
+            raise ValueError(f"GroupNorm: {groups} groups do not divide {c} channels")
+        self.c, self.groups, self.relu = c, groups, relu
+
+    def register(self, layout):
+        self.gamma = layout.add(f"{self.name}.weight", (self.c,), "ones", 1, self.name).name
+        self.beta = layout.add(f"{self.name}.bias", (self.c,), "zeros", 1, self.name).name
+
+    def own_params(self):
+        return [self.gamma, self.beta]
+
+    def forward(self, x, ctx, residual=None, relu=None, link=None, planes: int = 0):
+        """`planes`: BatchNorm.forward's codes, so one block definition serves both norms. Every
+        code whose readers include a split-plane conv (1, 2, 3, 5) gives fp32 + planes here (no
+        planes-only or deferred forms); 0 and 4 (read only as a residual) give fp32."""
+        P = ctx.P
+        want = planes not in (0, 4) and getattr(P, "split", None) is not None and self.c % 32 == 0
+        return Fn.group_norm(x, ctx.token, P.w(self.gamma), P.w(self.beta), P.g(self.gamma), P.g(self.beta),
+                             self.groups, ctx.valid, self.relu if relu is None else relu, residual, link=link,
+                             planes=want)
+
+
+def conv_bn(conv: Conv2d, bn: "BatchNorm | GroupNorm", x, ctx, conv_link=None, conv_donor=None, **bn_kw):
     """conv → BatchNorm with the BN statistics taken from the conv's epilogue (Fn.BNStats) and,
-    for fp32 split-plane GEMMs, the BN backward handing the conv only dX's planes."""
+    for fp32 split-plane GEMMs, the BN backward handing the conv only dX's planes. A GroupNorm in
+    the BatchNorm's place runs unfused: plain conv, then the norm."""
+    if isinstance(bn, GroupNorm):
+        return bn.forward(conv.forward(x, ctx, link=conv_link, donor=conv_donor), ctx, **bn_kw)
     st = Fn.BNStats(ctx.valid)
     return bn.forward(conv.forward(x, ctx, link=conv_link, stats=st, donor=conv_donor), ctx, stats=st, **bn_kw)
 

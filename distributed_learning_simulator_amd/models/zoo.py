@@ -14,7 +14,7 @@ import torch
 
 from ..engine.params import ParamLayout
 from ..ops import functional as Fn
-from .layers import (AvgPool, BatchNorm, Conv2d, Embedding, conv_bn, Flatten, LayerNorm, Linear,
+from .layers import (AvgPool, BatchNorm, Conv2d, Embedding, conv_bn, Flatten, GroupNorm, LayerNorm, Linear,
                      MaxPool, Module, ReLU, RunCtx, Seq)
 
 
@@ -108,15 +108,15 @@ class BasicBlock(Module):
     kind = "BasicBlock"
     expansion = 1
 
-    def __init__(self, cin, cout, stride):
+    def __init__(self, cin, cout, stride, norm=BatchNorm):
         super().__init__()
         self.child("conv1", Conv2d(cin, cout, 3, stride, 1))
-        self.child("bn1", BatchNorm(cout, relu=True))
+        self.child("bn1", norm(cout, relu=True))
         self.child("conv2", Conv2d(cout, cout, 3, 1, 1))
-        self.child("bn2", BatchNorm(cout))
+        self.child("bn2", norm(cout))
         self.down = None
         if stride != 1 or cin != cout:
-            self.down = self.child("downsample", Seq(Conv2d(cin, cout, 1, stride, 0), BatchNorm(cout)))
+            self.down = self.child("downsample", Seq(Conv2d(cin, cout, 1, stride, 0), norm(cout)))
 
     def forward(self, x, ctx, out_planes: int = 1):
         """`out_planes`: what reads the block output (ResNetNet.forward) — 1: the next block's convs
@@ -135,18 +135,18 @@ class Bottleneck(Module):
     kind = "Bottleneck"
     expansion = 4
 
-    def __init__(self, cin, width, stride):
+    def __init__(self, cin, width, stride, norm=BatchNorm):
         super().__init__()
         cout = width * 4
         self.child("conv1", Conv2d(cin, width, 1, 1, 0))
-        self.child("bn1", BatchNorm(width, relu=True))
+        self.child("bn1", norm(width, relu=True))
         self.child("conv2", Conv2d(width, width, 3, stride, 1))
-        self.child("bn2", BatchNorm(width, relu=True))
+        self.child("bn2", norm(width, relu=True))
         self.child("conv3", Conv2d(width, cout, 1, 1, 0))
-        self.child("bn3", BatchNorm(cout))
+        self.child("bn3", norm(cout))
         self.down = None
         if stride != 1 or cin != cout:
-            self.down = self.child("downsample", Seq(Conv2d(cin, cout, 1, stride, 0), BatchNorm(cout)))
+            self.down = self.child("downsample", Seq(Conv2d(cin, cout, 1, stride, 0), norm(cout)))
 
     def forward(self, x, ctx, out_planes: int = 1):
         """`out_planes`: as BasicBlock.forward."""
@@ -161,14 +161,17 @@ class Bottleneck(Module):
 class ResNetNet(Module):
     kind = "ResNet"
 
-    def __init__(self, block, layers, classes=10, cin=3, cifar_stem=True):
+    def __init__(self, block, layers, classes=10, cin=3, cifar_stem=True, norm=BatchNorm):
+        """`norm(c, relu=False)` builds every normalisation layer (_norm_factory): BatchNorm, or
+        GroupNorm under the same module names (`bn1`, `downsample.1`, …, as torchvision's
+        `norm_layer=` keeps them), so the flat parameter layout is the BatchNorm model's."""
         super().__init__()
         self.cifar_stem = cifar_stem
         if cifar_stem:
             self.child("conv1", Conv2d(cin, 64, 3, 1, 1))
         else:
             self.child("conv1", Conv2d(cin, 64, 7, 2, 3))
-        self.child("bn1", BatchNorm(64, relu=True))
+        self.child("bn1", norm(64, relu=True))
         if not cifar_stem:
             self.child("maxpool", MaxPool(3, 2, 1))
         c = 64
@@ -177,7 +180,7 @@ class ResNetNet(Module):
             blocks = []
             for j in range(n):
                 stride = 2 if (j == 0 and i > 0) else 1
-                b = block(c, w, stride)
+                b = block(c, w, stride, norm)
                 blocks.append(b)
                 c = w * block.expansion
             self.stages.append(self.child(f"layer{i + 1}", Seq(*blocks)))
@@ -487,6 +490,28 @@ class GCNNet(Module):
 
 
 # --------------------------------------------------------------------------- build
+NORMS = ("batch", "group")
+
+
+def _norm_factory(kw: dict, model: str):
+    """`model_kwargs.norm`: `batch` (default) or `group`; `model_kwargs.gn_groups` (default 2, the
+    federated ResNet-18-GN setting of Hsieh et al. 2020 / Reddi et al. 2021; 32 is Wu & He's): any
+    G that divides every normalised width of the model."""
+    norm = str(kw.get("norm", "batch")).lower()
+    if norm not in NORMS:
+        raise ValueError(f"model_kwargs.norm must be one of {NORMS}, got {kw.get('norm')!r}")
+    if norm == "batch":
+        return BatchNorm
+    groups = int(kw.get("gn_groups", 2))
+
+    def make(c, relu=False):
+        if groups < 1 or c % groups:
+            raise ValueError(f"model_kwargs.gn_groups={groups} does not divide the {c}-channel layers of {model}")
+        return GroupNorm(c, groups, relu=relu)
+
+    return make
+
+
 def count_params(model: CohortModel) -> int:
     return model.layout.num_params
 
@@ -519,8 +544,12 @@ def build_model(name: str, dataset_spec, model_kwargs: dict | None = None) -> Co
             cfg = {18: (BasicBlock, [2, 2, 2, 2]), 34: (BasicBlock, [3, 4, 6, 3]),
                    50: (Bottleneck, [3, 4, 6, 3]), 101: (Bottleneck, [3, 4, 23, 3])}[depth]
             cifar = kw.get("cifar_stem", H <= 64)
-            return CohortModel(ResNetNet(cfg[0], cfg[1], classes, C, cifar), name, "image", classes)
+            return CohortModel(ResNetNet(cfg[0], cfg[1], classes, C, cifar, _norm_factory(kw, name)), name, "image",
+                               classes)
         if n.startswith("densenet"):
+            if _norm_factory(kw, name) is not BatchNorm:
+                raise ValueError(f"model_kwargs.norm=group is not available for {name}: its fused dense block "
+                                 "is BatchNorm-specific (ResNet-18/34/50/101 take it)")
             depth = int(n[8:] or 40)
             return CohortModel(DenseNetNet(depth, kw.get("growth_rate", 12), classes, C), name, "image", classes)
     if dataset_spec.kind == "text":

@@ -1018,6 +1018,58 @@ def layer_norm(x, token, gamma, beta, ggamma, gbeta, planes: bool = False):
     return _LN.apply(x, token, gamma, beta, ggamma, gbeta, planes)
 
 
+# ------------------------------------------------------------------------ groupnorm
+class _GN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, token, gamma, beta, ggamma, gbeta, G, valid, relu, residual, link=None, planes=False):
+        be = _be(x)
+        _require_fp32(x, "group_norm")
+        x = x.contiguous()
+        res = None
+        if residual is not None:
+            _require_fp32(residual, "group_norm residual")
+            res = residual.contiguous()
+        yp = None
+        if (planes and OPTIONS.planes and be is not ref and x.dtype == torch.float32
+                and be.planes_fit(x[0].numel())):
+            y, mean, rstd, yp = be.gn_fwd(x, gamma, beta, G, valid, relu, res, planes=True)
+        else:
+            y, mean, rstd = be.gn_fwd(x, gamma, beta, G, valid, relu, res)
+        # (y is read by the backward only for the ReLU gate y > 0)
+        ctx.save_for_backward(x, y if relu else None, mean, rstd, gamma)
+        ctx.G, ctx.valid, ctx.relu, ctx.has_res, ctx.link = G, valid, relu, residual is not None, link
+        ctx.ggamma, ctx.gbeta = ggamma, gbeta
+        if yp is not None:
+            _tag_planes(y, yp, False)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, mean, rstd, gamma = ctx.saved_tensors
+        be = _be(dy)
+        _require_fp32(dy, "group_norm backward")
+        dx, dgamma, dbeta, dres = be.gn_bwd(dy.contiguous(), x, y, mean, rstd, gamma, ctx.G, ctx.valid, ctx.relu,
+                                            ctx.has_res)
+        if ctx.ggamma is not None:
+            ctx.ggamma.copy_(dgamma)
+            ctx.gbeta.copy_(dbeta)
+        if dres is not None and ctx.link is not None:
+            ctx.link.grad = dres  # delivered by the block's first conv (ResidualLink), as _BN does
+            dres = None
+        return dx, None, None, None, None, None, None, None, None, dres, None, None
+
+
+def group_norm(x, token, gamma, beta, ggamma, gbeta, G: int, valid=None, relu=False, residual=None,
+               link: ResidualLink | None = None, planes: bool = False):
+    """GroupNorm over G groups of adjacent channels of x [K, B, ..., C], one statistic per (client,
+    sample, group), then + `residual`, then ReLU (ops.ref.gn_fwd is the contract). `valid` [K]: the
+    samples b >= valid[k] are not read and come out as zeros. `link`: the residual's gradient is
+    deposited there for the block's first conv instead of returned to autograd (as batch_norm).
+    `planes` (fp32 native): the output also carries its split planes (`_dls_planes`) for the
+    split-plane convs that read it."""
+    return _GN.apply(x, token, gamma, beta, ggamma, gbeta, G, valid, relu, residual, link, planes)
+
+
 # -------------------------------------------------------------------------- pooling
 class _MaxPool(torch.autograd.Function):
     @staticmethod

@@ -1210,6 +1210,80 @@ def ln_bwd(dy, x, mean, rstd, gamma):
     return dx, dgamma, dbeta
 
 
+# ------------------------------------------------------------------------ groupnorm
+def _gn_shape(x, G: int):
+    """(K, B, HW, C) of a channels-last activation [K, B, ..., C] whose C channels form G groups."""
+    assert x.dim() >= 3, "group norm input is [K, B, ..., C]"
+    K, B, C = x.shape[0], x.shape[1], x.shape[-1]
+    HW = x.numel() // max(K * B * C, 1)
+    assert G > 0 and C % G == 0, f"{G} groups do not divide {C} channels"
+    assert _C.gn_shape_ok(HW, C, G), f"group norm shape out of range: HW={HW} C={C} G={G}"
+    return K, B, HW, C
+
+
+def _gn_valid(valid, K: int):
+    if valid is None:
+        return None
+    assert valid.shape == (K,) and valid.is_cuda
+    return valid.to(torch.int32).contiguous()
+
+
+def gn_workspace_floats(K: int, B: int, C: int) -> int:
+    """Floats of the per-sample dγ / dβ rows gn_bwd folds (held in the `_tn_part` buffer)."""
+    return _C.gn_workspace_floats(K, B, C)
+
+
+def gn_fwd(x, gamma, beta, G: int, valid=None, relu=False, residual=None, eps=1e-5, planes: bool = False):
+    """GroupNorm of x [K, B, ..., C] (contract: ops.ref.gn_fwd), one workgroup per sample. Returns
+    (y, mean [K, B, G], rstd [K, B, G]); `planes` (fp32) also writes y's split planes
+    [K, 2, B, ..., C], returned fourth. Samples b >= valid[k] are not read."""
+    K, B, HW, C = _gn_shape(x, G)
+    _check(x, name="x")
+    g_cs, rep = _client_view(gamma, K)
+    assert _client_view(beta, K) == (g_cs, rep), "γ and β must be views of the same layout"
+    assert gamma.dtype == x.dtype == beta.dtype and gamma.shape[-1] == C == beta.shape[-1]
+    if residual is not None:
+        _check(residual, x.dtype, name="residual")
+        assert residual.shape == x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty((K, B, G), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((K, B, G), dtype=torch.float32, device=x.device)
+    yp = None
+    if planes and x.dtype == F32:
+        yp = torch.empty((K, 2) + tuple(x.shape[1:]), dtype=BF16, device=x.device)
+        assert yp.stride(1) * 4 < 2 ** 31, "per-client plane window over 2 GiB"
+    _C.gn_fwd(_p(x), _p(residual), _p(gamma), _p(beta), _p(y), _p(yp), _p(mean), _p(rstd), _p(_gn_valid(valid, K)),
+              g_cs, rep, K, B, HW, C, G, eps, int(bool(relu)), _f32(x), _s())
+    if planes:
+        return y, mean, rstd, yp
+    return y, mean, rstd
+
+
+def gn_bwd(dy, x, y, mean, rstd, gamma, G: int, valid=None, relu=False, need_dres=False):
+    """Returns (dx, dgamma [K, C], dbeta [K, C], dres) (contract: ops.ref.gn_bwd). `y` is read only
+    with `relu`, for the gate y > 0. dγ / dβ are per-sample rows folded over b < valid[k] in
+    ascending order: bitwise reproducible in every mode, no atomics."""
+    K, B, HW, C = _gn_shape(x, G)
+    _check(x, name="x")
+    dy = dy.contiguous()
+    _check(dy, x.dtype, name="dy")
+    assert dy.shape == x.shape and mean.shape == (K, B, G) == rstd.shape
+    assert mean.dtype == F32 == rstd.dtype and mean.is_contiguous() and rstd.is_contiguous()
+    g_cs, rep = _client_view(gamma, K)
+    assert gamma.dtype == x.dtype and gamma.shape[-1] == C
+    if relu:
+        _check(y, x.dtype, name="y")
+        assert y.shape == x.shape
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if need_dres else None
+    dgamma = torch.empty((K, C), dtype=torch.float32, device=x.device)
+    dbeta = torch.empty((K, C), dtype=torch.float32, device=x.device)
+    ws = _tn_part(gn_workspace_floats(K, B, C), x.device)
+    _C.gn_bwd(_p(dy), _p(x), _p(y if relu else None), _p(mean), _p(rstd), _p(gamma), _p(_gn_valid(valid, K)), g_cs,
+              rep, K, B, HW, C, G, int(bool(relu)), _p(dx), _p(dres), _p(dgamma), _p(dbeta), C, _p(ws), _f32(x), _s())
+    return dx, dgamma, dbeta, dres
+
+
 # -------------------------------------------------------------------------- pooling
 def _pool_fwd(x, k, s, pad, mode):
     K, B, H, W, C = x.shape

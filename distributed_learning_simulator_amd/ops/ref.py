@@ -232,6 +232,78 @@ def ln_bwd(dy, x, mean, rstd, gamma):
     return dx.to(x.dtype), dgamma, dbeta
 
 
+# ------------------------------------------------------------------------ group norm
+def _sample_mask(x, valid):
+    """[K, B, 1, ..., 1] bool: sample b of client k is real (b < valid[k]); None without `valid`."""
+    if valid is None:
+        return None
+    K, B = x.shape[:2]
+    m = torch.arange(B, device=x.device)[None, :] < valid.to(x.device)[:, None]
+    return m.view((K, B) + (1,) * (x.dim() - 2))
+
+
+def _gn_params(p, K: int, dim: int):
+    p = _match(p, K).float()
+    return p.reshape((K,) + (1,) * (dim - 2) + (p.shape[-1],))
+
+
+def gn_fwd(x, gamma, beta, G: int, valid=None, relu=False, residual=None, eps=1e-5):
+    """GroupNorm of channels-last x [K, B, ..., C]: G groups of C / G adjacent channels, one
+    (mean, biased two-pass variance) per (client, sample, group); then + residual, then ReLU.
+    `valid` [K]: samples b >= valid[k] are not read (they may hold anything, NaN included); their
+    y is +0 and their mean / rstd are 0. Returns (y, mean [K, B, G], rstd [K, B, G])."""
+    K, B, C = x.shape[0], x.shape[1], x.shape[-1]
+    assert C % G == 0, (C, G)
+    m = _sample_mask(x, valid)
+    xf = x.float()
+    if m is not None:
+        xf = torch.where(m, xf, torch.zeros((), device=x.device))
+    xg = xf.reshape(K, B, -1, G, C // G)
+    mean = xg.mean(dim=(2, 4))
+    var = ((xg - mean[:, :, None, :, None]) ** 2).mean(dim=(2, 4))
+    rstd = torch.rsqrt(var + eps)
+    xhat = ((xg - mean[:, :, None, :, None]) * rstd[:, :, None, :, None]).reshape(x.shape)
+    y = xhat * _gn_params(gamma, K, x.dim()) + _gn_params(beta, K, x.dim())
+    if residual is not None:
+        y = y + residual.float()
+    if relu:
+        y = torch.relu(y)
+    if m is not None:
+        zero = torch.zeros((), device=x.device)
+        y = torch.where(m, y, zero)
+        mean = torch.where(m.view(K, B, 1), mean, zero)
+        rstd = torch.where(m.view(K, B, 1), rstd, zero)
+    return y.to(x.dtype), mean, rstd
+
+
+def gn_bwd(dy, x, y, mean, rstd, gamma, G: int, valid=None, relu=False, need_dres=False):
+    """Returns (dx, dgamma [K, C], dbeta [K, C], dres): ĝ = dy·[y > 0] with ReLU (`y` may be the
+    output or any tensor positive exactly where it is), dres = ĝ (None unless `need_dres`). Samples
+    b >= valid[k] are not read: dx = dres = +0 there and they add nothing to dγ / dβ."""
+    K, B, C = x.shape[0], x.shape[1], x.shape[-1]
+    m = _sample_mask(x, valid)
+    g = dy.float()
+    xf = x.float()
+    if relu:
+        g = g * (y.float() > 0)
+    if m is not None:
+        zero = torch.zeros((), device=x.device)
+        g = torch.where(m, g, zero)
+        xf = torch.where(m, xf, zero)
+    xhat = ((xf.reshape(K, B, -1, G, C // G) - mean[:, :, None, :, None]) * rstd[:, :, None, :, None]).reshape(x.shape)
+    red = tuple(range(1, x.dim() - 1))
+    dgamma = (g * xhat).sum(dim=red)
+    dbeta = g.sum(dim=red)
+    gg = (g * _gn_params(gamma, K, x.dim())).reshape(K, B, -1, G, C // G)
+    xh = xhat.reshape(K, B, -1, G, C // G)
+    dx = rstd[:, :, None, :, None] * (gg - gg.mean(dim=(2, 4), keepdim=True)
+                                      - xh * (gg * xh).mean(dim=(2, 4), keepdim=True))
+    dx = dx.reshape(x.shape)
+    if m is not None:
+        dx = torch.where(m, dx, zero)
+    return dx.to(x.dtype), dgamma, dbeta, (g.to(x.dtype) if need_dres else None)
+
+
 # -------------------------------------------------------------------------- pooling
 def maxpool_fwd(x, k: int, s: int, pad: int = 0):
     K, B, H, W, C = x.shape

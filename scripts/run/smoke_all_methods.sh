@@ -58,5 +58,11 @@ $S --config-name fed_secagg/mnist.yaml ++fed_secagg.round=2 ++fed_secagg.epoch=1
 $S --config-name fed_secagg/mnist.yaml ++fed_secagg.round=2 ++fed_secagg.epoch=1 ++fed_secagg.worker_number=6 \
    ++fed_secagg.algorithm_kwargs.secagg_degree=2 ++fed_secagg.algorithm_kwargs.secagg_threshold=1 \
    ++fed_secagg.algorithm_kwargs.failure_rate=0.2 ++fed_secagg.debug=True
+# ResNet-18 with GroupNorm in place of BatchNorm (model_kwargs.norm: group) on non-IID shards, under
+# FedAvg and under a server optimiser (FedAdam, two rounds so that the second steps on non-zero state)
+$S --config-name fed_avg/cifar10_gn.yaml ++fed_avg.round=1 ++fed_avg.epoch=1 ++fed_avg.worker_number=4 \
+   ++fed_avg.dataset_kwargs.scale=0.01 ++fed_avg.debug=True
+$S --config-name fed_adam/cifar10_gn.yaml ++fed_adam.round=2 ++fed_adam.epoch=1 ++fed_adam.worker_number=4 \
+   ++fed_adam.algorithm_kwargs.random_client_number=4 ++fed_adam.dataset_kwargs.scale=0.01 ++fed_adam.debug=True
 # sign-SGD (1-bit majority vote)
 $S --config-name sign_sgd/cifar10.yaml ++sign_sgd.round=1 ++sign_sgd.epoch=1 ++sign_sgd.worker_number=4
