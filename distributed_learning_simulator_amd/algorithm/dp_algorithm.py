@@ -34,7 +34,8 @@ import statistics
 
 import torch
 
-from ..message import CohortMessage, FlatParameterMessage
+from ..config import clients_per_round
+from ..message import CohortMessage
 from ..ops import fl
 from ..utils import privacy
 from ..utils.logging import get_logger
@@ -67,15 +68,12 @@ class DPFedAvgAlgorithm(FedAVGAlgorithm):
         self.clip, self.noise_multiplier, self.delta = 1.0, 1.0, 1e-5
         self._nsq: list[torch.Tensor] = []  # this round's squared norms, one device tensor per message
         self._ids: list[int] = []  # ... and the client ids, in the same order
-        self._rounds_done = 0  # (round index when no server is bound: unit tests)
         self._rdp: tuple[list[float], list[float]] | None = None  # RDP curves at q = 1 and q = m / N
         self._mask: torch.Tensor | None = None
         self.last_norms: dict[int, float] = {}  # client id -> L2 norm of its upload (all ranks)
         self.last_clipped: list[int] = []  # client ids whose upload was scaled down
         self.last_rejected: list[int] = []  # client ids whose upload was not finite
         self.last_acc: torch.Tensor | None = None  # the fp64 accumulator after the noise
-        self.last_fp64: torch.Tensor | None = None
-        self.round_stats: dict = {}
 
     def bind(self, config, layout, device, comm=None, server=None) -> None:
         super().bind(config, layout, device, comm, server)
@@ -86,12 +84,7 @@ class DPFedAvgAlgorithm(FedAVGAlgorithm):
     # ------------------------------------------------------------------ settings
     def denominator(self) -> int:
         """The fixed m of the mean: `random_client_number` if set, else `worker_number`."""
-        n = int(self.config.worker_number)
-        m = self.config.algorithm_kwargs.get("random_client_number", None)
-        return min(int(m), n) if m else n
-
-    def _round(self) -> int:
-        return int(self.server.round_number) if self.server is not None else self._rounds_done + 1
+        return clients_per_round(self.config.algorithm_kwargs, self.config.worker_number)
 
     def _valid_mask(self) -> torch.Tensor | None:
         if self._mask is None and hasattr(self.layout, "valid_mask"):
@@ -128,21 +121,14 @@ class DPFedAvgAlgorithm(FedAVGAlgorithm):
         self._ids.extend(int(c) for c in msg.client_ids)
         self._reported += len(msg.client_ids)
 
-    def _round_norms(self) -> dict[int, float]:
-        """client id -> squared norm over all ranks: ONE host read of this rank's n doubles."""
-        local = torch.cat(self._nsq).tolist() if self._nsq else []
-        pairs = list(zip(self._ids, local))
-        if self.comm.is_distributed:
-            pairs = [p for part in self.comm.all_gather_object(pairs) for p in part]
-        return dict(sorted(pairs))
-
-    def aggregate_worker_data(self, old_parameter: torch.Tensor) -> FlatParameterMessage:
+    def _aggregate(self, old: torch.Tensor) -> torch.Tensor:
         if self.expected_kind != "delta":
             raise RuntimeError("fed_dp_avg clips client deltas: the workers must upload parameter differences")
         self._ensure_acc()
         self._reduce()
-        acc, rnd, m = self._acc, self._round(), self.denominator()
-        nsq = self._round_norms()
+        acc, rnd, m = self._acc, self.round_index(), self.denominator()
+        # client id -> squared norm over all ranks: ONE host read of this rank's n doubles
+        nsq = {c: v for c, (v,) in self._gather_client_values(self._ids, self._nsq).items()}
         self.last_rejected = [c for c, v in nsq.items() if not math.isfinite(v)]
         self.last_norms = {c: math.sqrt(v) if math.isfinite(v) and v >= 0.0 else math.nan for c, v in nsq.items()}
         self.last_clipped = [c for c, v in self.last_norms.items() if v > self.clip]
@@ -150,8 +136,6 @@ class DPFedAvgAlgorithm(FedAVGAlgorithm):
             get_logger().warning("fed_dp_avg: rejected the non-finite uploads of clients %s", self.last_rejected)
         if self.noise_multiplier > 0.0:  # the same draw on every rank: keyed by (seed, round, position)
             fl.gaussian_add(acc, self.noise_multiplier * self.clip, int(self.config.seed), rnd, self._valid_mask())
-        old_dtype = old_parameter.dtype
-        old = old_parameter.to(self.device, torch.float64)
         new = old + acc / torch.full((), float(m), dtype=torch.float64, device=self.device)
         if not nsq:
             get_logger().warning("round without any client upload: the global model moves by the noise alone")
@@ -165,17 +149,9 @@ class DPFedAvgAlgorithm(FedAVGAlgorithm):
             "dp_epsilon_poisson": eps_poisson,
         }
         self.last_acc = acc
-        self.last_fp64 = new  # pre-cast fp64 result (tests)
-        new = new.to(old_dtype)
-        if self.config is not None and self.config.debug:
-            assert not torch.isnan(new).any(), "NaN in aggregated parameters"
-        msg = FlatParameterMessage(parameter=new, layout=self.layout, other_data=dict(self._other_data),
-                                   end_training=bool(self._end_training))
-        self._rounds_done += 1
-        self._reset_acc()
-        return msg
+        return new
 
-    def _reset_acc(self) -> None:
-        super()._reset_acc()
+    def _reset_round(self) -> None:
+        super()._reset_round()
         self._nsq = []
         self._ids = []

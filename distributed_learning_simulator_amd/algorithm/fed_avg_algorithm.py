@@ -17,13 +17,19 @@ Generalisations used by the methods:
 * element masks (`msg.mask`, FedDropoutAvg) → per-element weights (`_get_weight` analogue);
 * block masks (`msg.block_mask`, FedOBD stage 1) → per-block weights: a block is averaged
   over the clients that sent it; blocks no client sent keep θ_t (fixes B4).
+
+The round's frame (θ_t → fp64, `last_fp64`, the one cast, the NaN assertion, the result
+message, the reset) is `AggregationAlgorithm.aggregate_worker_data`; this class fills in
+`_process`, `_aggregate` and `_reset_round`. A method built on the fp64 accumulator (DP-FedAvg,
+secure aggregation, SCAFFOLD) overrides `_process` and `_aggregate`, calls `_ensure_acc()` and
+`_reduce()` for the accumulator and the cross-rank sum, and extends `_reset_round`.
 """
 
 from __future__ import annotations
 
 import torch
 
-from ..message import CohortMessage, FlatParameterMessage
+from ..message import CohortMessage
 from ..ops import fl
 from ..utils.logging import get_logger
 from .aggregation_algorithm import AggregationAlgorithm
@@ -117,19 +123,12 @@ class FedAVGAlgorithm(AggregationAlgorithm):
         if flags is not None:
             end, other, reported = flags.tolist()
             self._reported = int(reported)
-            if end > 0:
-                self._end_training = True
-            if other > 0:  # end_training / other_data must agree on every server replica
-                for _, od in comm.all_gather_object((self._end_training, self._other_data)):
-                    for k, v in od.items():
-                        self._other_data.setdefault(k, v)
+            self._merge_round_flags(end > 0, other > 0)
 
-    def aggregate_worker_data(self, old_parameter: torch.Tensor) -> FlatParameterMessage:
+    def _aggregate(self, old: torch.Tensor) -> torch.Tensor:
         self._ensure_acc()
         self._reduce()
         acc = self._acc
-        old_dtype = old_parameter.dtype
-        old = old_parameter.to(self.device, torch.float64)
         zero = torch.zeros((), dtype=torch.float64, device=self.device)
         if self._w_elem is not None:
             den = self._w_elem
@@ -155,23 +154,12 @@ class FedAVGAlgorithm(AggregationAlgorithm):
                 new = torch.where(wt > 0, acc / wt.clamp(min=1e-300), old)
             if self._reported == 0:  # (host-side count: no device read)
                 get_logger().warning("round without any weighted client upload: global model unchanged")
-        self.last_fp64 = new  # pre-cast fp64 result (golden tests)
-        new = new.to(old_dtype)
-        if self.config is not None and self.config.debug:
-            assert not torch.isnan(new).any(), "NaN in aggregated parameters"
-        msg = FlatParameterMessage(parameter=new, layout=self.layout, other_data=dict(self._other_data),
-                                   end_training=bool(self._end_training))
-        self._reset_acc()
-        return msg
+        return new
 
-    def _reset_acc(self) -> None:
+    def _reset_round(self) -> None:
         self._reported = 0
         self._acc = None
         self._w_total = None
         self._w_elem = None
         self._w_block = None
         self._kind = None
-
-    def clear_worker_data(self) -> None:
-        super().clear_worker_data()
-        self._reset_acc()

@@ -22,7 +22,6 @@ from __future__ import annotations
 
 import torch
 
-from ..message import FlatParameterMessage
 from ..ops import fl
 from ..utils.logging import get_logger
 from .robust_algorithm import TrimmedMeanAlgorithm
@@ -50,13 +49,11 @@ class MultiKrumAlgorithm(TrimmedMeanAlgorithm):
     def krum_m(self, n: int, f: int) -> int:
         return 1 if self.single else int(self._kw("krum_m", n - f))
 
-    def aggregate_worker_data(self, old_parameter: torch.Tensor) -> FlatParameterMessage:
+    def _aggregate(self, old: torch.Tensor) -> torch.Tensor:
         kind = self._kind or self.expected_kind
         rows = self._gather_rows()
         ids = self._round_ids
         n = rows.shape[0]
-        old_dtype = old_parameter.dtype
-        old = old_parameter.to(self.device, torch.float64)
         self.last_selected, self.last_scores, self.last_dists, self.last_ids = [], {}, None, list(ids)
         if n == 0:
             get_logger().warning("round without any weighted client upload: global model unchanged")
@@ -78,14 +75,7 @@ class MultiKrumAlgorithm(TrimmedMeanAlgorithm):
                 upd = fl.weighted_sum(picked, ones) / float(len(sel))
             new = old + upd if kind == "delta" else upd
         self.last_trim = (n, 0)
-        self.last_fp64 = new  # pre-cast fp64 result (tests)
-        new = new.to(old_dtype)
-        if self.config is not None and self.config.debug:
-            assert not torch.isnan(new).any(), "NaN in aggregated parameters"
-        msg = FlatParameterMessage(parameter=new, layout=self.layout, other_data=dict(self._other_data),
-                                   end_training=bool(self._end_training))
-        self._reset_round()
-        return msg
+        return new
 
 
 class KrumAlgorithm(MultiKrumAlgorithm):

@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import torch
 
-from ..message import CohortMessage, FlatParameterMessage
+from ..message import CohortMessage
 from ..ops import fl
 from ..utils.logging import get_logger
 from .aggregation_algorithm import AggregationAlgorithm
@@ -41,7 +41,6 @@ class TrimmedMeanAlgorithm(AggregationAlgorithm):
         self._ids: list[int] = []  # their client ids, in row order
         self._round_ids: list[int] = []  # ids of the rows `_gather_rows` returned (track_ids)
         self._kind: str | None = None
-        self.last_fp64: torch.Tensor | None = None
         self.last_trim: tuple[int, int] = (0, 0)  # (n, b) of the last aggregation
 
     # ------------------------------------------------------------------ round store
@@ -83,12 +82,7 @@ class TrimmedMeanAlgorithm(AggregationAlgorithm):
                             dtype=torch.int64, device=self.device)
         heads = torch.stack(comm.all_gather(head)).tolist()
         counts = [int(h[0]) for h in heads]
-        if any(h[1] for h in heads):
-            self._end_training = True
-        if any(h[2] for h in heads):  # end_training / other_data must agree on every server replica
-            for _, od in comm.all_gather_object((self._end_training, self._other_data)):
-                for k, v in od.items():
-                    self._other_data.setdefault(k, v)
+        self._merge_round_flags(any(h[1] for h in heads), any(h[2] for h in heads))
         m = max(counts)
         if m == 0:
             return local
@@ -115,12 +109,10 @@ class TrimmedMeanAlgorithm(AggregationAlgorithm):
             return med
         return b
 
-    def aggregate_worker_data(self, old_parameter: torch.Tensor) -> FlatParameterMessage:
+    def _aggregate(self, old: torch.Tensor) -> torch.Tensor:
         kind = self._kind or self.expected_kind
         rows = self._gather_rows()
         n = rows.shape[0]
-        old_dtype = old_parameter.dtype
-        old = old_parameter.to(self.device, torch.float64)
         if n == 0:
             # every selected client failed / skipped: keep θ_t
             get_logger().warning("round without any weighted client upload: global model unchanged")
@@ -130,23 +122,12 @@ class TrimmedMeanAlgorithm(AggregationAlgorithm):
             mean = fl.trimmed_sum(rows, b) / float(n - 2 * b)
             new = old + mean if kind == "delta" else mean
         self.last_trim = (n, b)
-        self.last_fp64 = new  # pre-cast fp64 result (tests)
-        new = new.to(old_dtype)
-        if self.config is not None and self.config.debug:
-            assert not torch.isnan(new).any(), "NaN in aggregated parameters"
-        msg = FlatParameterMessage(parameter=new, layout=self.layout, other_data=dict(self._other_data),
-                                   end_training=bool(self._end_training))
-        self._reset_round()
-        return msg
+        return new
 
     def _reset_round(self) -> None:
         self._n = 0
         self._ids = []
         self._kind = None
-
-    def clear_worker_data(self) -> None:
-        super().clear_worker_data()
-        self._reset_round()
 
 
 class MedianAlgorithm(TrimmedMeanAlgorithm):

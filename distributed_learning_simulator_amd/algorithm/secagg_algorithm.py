@@ -34,7 +34,8 @@ from __future__ import annotations
 
 import torch
 
-from ..message import CohortMessage, FlatParameterMessage
+from ..config import clients_per_round
+from ..message import CohortMessage
 from ..ops import compress, fl
 from ..utils.logging import get_logger
 from ..utils.secagg_protocol import mask_graph, round_protocol
@@ -42,10 +43,8 @@ from .fed_avg_algorithm import FedAVGAlgorithm
 
 
 def cohort_size(config) -> int:
-    """The fixed m: `random_client_number` if set, else `worker_number` (the rule of DP-FedAvg's denominator)."""
-    n = int(config.worker_number)
-    m = config.algorithm_kwargs.get("random_client_number", None)
-    return min(int(m), n) if m else n
+    """The fixed m: `random_client_number` if set, else `worker_number`."""
+    return clients_per_round(config.algorithm_kwargs, config.worker_number)
 
 
 def secagg_settings(config) -> tuple[float, int, int, int | None]:
@@ -73,20 +72,14 @@ class SecAggAlgorithm(FedAVGAlgorithm):
         self.range, self.frac_bits, self.degree, self.threshold = 1.0, 1, 0, None
         self._ids: list[int] = []  # this round's reporting clients on this rank, in upload order
         self._counters: list[torch.Tensor] = []  # ... and their (clamped, NaN) counters, one tensor per message
-        self._rounds_done = 0
         self._valid = 0
         self.last_reporting: list[int] = []
         self.last_dropped: list[int] = []
-        self.last_fp64: torch.Tensor | None = None
-        self.round_stats: dict = {}
 
     def bind(self, config, layout, device, comm=None, server=None) -> None:
         super().bind(config, layout, device, comm, server)
         self.range, self.frac_bits, self.degree, self.threshold = secagg_settings(config)
         self._valid = int(layout.num_params)
-
-    def _round(self) -> int:
-        return int(self.server.round_number) if self.server is not None else self._rounds_done + 1
 
     def _selected(self) -> list[int]:
         return list(self.server.selected) if self.server is not None else sorted(self.last_reporting)
@@ -116,30 +109,21 @@ class SecAggAlgorithm(FedAVGAlgorithm):
         self._counters.append(msg.extra["secagg_stats"])
         self._reported += len(msg.client_ids)
 
-    def _gather_reports(self) -> dict[int, tuple[int, int]]:
-        """client id -> (clamped, NaN) over all ranks: one host read of this rank's counters, one gather."""
-        local = torch.cat(self._counters).tolist() if self._counters else []
-        pairs = [(c, int(v[0]), int(v[1])) for c, v in zip(self._ids, local)]
-        if self.comm.is_distributed:
-            pairs = [p for part in self.comm.all_gather_object(pairs) for p in part]
-        return {c: (a, b) for c, a, b in sorted(pairs)}
-
-    def aggregate_worker_data(self, old_parameter: torch.Tensor) -> FlatParameterMessage:
+    def _aggregate(self, old: torch.Tensor) -> torch.Tensor:
         if self.expected_kind != "delta":
             raise RuntimeError("fed_secagg masks client deltas: the workers must upload parameter differences")
         self._ensure_acc()
-        reports = self._gather_reports()
+        # client id -> (clamped, NaN) over all ranks: one host read of this rank's counters, one gather
+        reports = self._gather_client_values(self._ids, self._counters)
         self._reduce()  # one int64 all-reduce of the accumulator (+ the round flags)
         S = sorted(reports)
         selected = sorted(set(self._selected()) | set(S))
-        proto = round_protocol(self.config.seed, self._round(), selected, self.degree, self.threshold)
+        proto = round_protocol(self.config.seed, self.round_index(), selected, self.degree, self.threshold)
         D = [c for c in proto.ids if c not in reports]
         keys, signs, aborted = proto.recover(S)
-        old_dtype = old_parameter.dtype
-        old = old_parameter.to(self.device, torch.float64)
         if aborted:
             get_logger().warning("fed_secagg: round %d aborted, too few shares survive (reporting %s, dropped %s): "
-                                 "global model unchanged", self._round(), S, D)
+                                 "global model unchanged", self.round_index(), S, D)
             new = old.clone()
         elif not S:
             get_logger().warning("round without any client upload: global model unchanged")
@@ -160,17 +144,9 @@ class SecAggAlgorithm(FedAVGAlgorithm):
             "secagg_mask_streams": sum(len(proto.client_entries(c)) for c in S) + len(keys),
             "secagg_dropped_bytes": sum(proto.dropped_bytes(c) for c in D),
         }
-        self.last_fp64 = new  # pre-cast fp64 result (tests, the server optimiser)
-        new = new.to(old_dtype)
-        if self.config is not None and self.config.debug:
-            assert not torch.isnan(new).any(), "NaN in aggregated parameters"
-        msg = FlatParameterMessage(parameter=new, layout=self.layout, other_data=dict(self._other_data),
-                                   end_training=bool(self._end_training))
-        self._rounds_done += 1
-        self._reset_acc()
-        return msg
+        return new
 
-    def _reset_acc(self) -> None:
-        super()._reset_acc()
+    def _reset_round(self) -> None:
+        super()._reset_round()
         self._ids = []
         self._counters = []

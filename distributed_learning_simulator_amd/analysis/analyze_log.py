@@ -25,6 +25,8 @@ import argparse
 import re
 import statistics
 
+from ..config import clients_per_round
+
 _NUM = r"([0-9.eE+-]+)"
 _TEST = re.compile(r"round: (\d+), test accuracy " + _NUM)
 _WORKER_ACC = re.compile(r"worker (\d+) round \d+ train loss \S+ accuracy " + _NUM)
@@ -81,7 +83,7 @@ def compute_data_amount(config, paths: list[str], num_params: int | None = None,
                                  config.model_kwargs).num_params
     P, W, R = num_params, config.worker_number, config.round
     ak = config.algorithm_kwargs
-    sel = min(int(ak.get("random_client_number", W) or W), W)  # as the server samples (Session)
+    sel = clients_per_round(ak, W)  # as the server samples (Session)
     up_msgs = R * sel
     up_params = up_msgs * P
     down_params = up_params

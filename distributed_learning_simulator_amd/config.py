@@ -148,6 +148,15 @@ class DistributedTrainingConfig:
 global_config: DistributedTrainingConfig = DistributedTrainingConfig()
 
 
+def clients_per_round(algorithm_kwargs: dict, worker_number: int) -> int:
+    """The fixed number of clients a round selects: `random_client_number` if set (capped at
+    `worker_number`), else `worker_number`. Takes the two values, not a config object, so that it
+    also serves a dict loaded from `config.json` (analysis)."""
+    W = int(worker_number)
+    m = algorithm_kwargs.get("random_client_number")
+    return min(int(m), W) if m else W
+
+
 # ---------------------------------------------------------------------- YAML helpers
 def _read_yaml(path: str) -> dict:
     with open(path, encoding="utf8") as f:

@@ -149,3 +149,13 @@ class CohortMessage(Message):
         if self.kind == "delta":
             return DeltaParameterMessage(delta_parameter=tensors, **common)
         return ParameterMessage(parameter=tensors, **common)
+
+
+def attach_payload(msg: CohortMessage, payload, decode_into: bool = True) -> CohortMessage:
+    """The upload becomes the packed payload: the dense rows are no longer part of the message,
+    kept only as the receiver's decode target (`CohortMessage.dense`) unless `decode_into` is off."""
+    msg.payload = payload
+    if decode_into:
+        msg.extra["decode_into"] = msg.data
+    msg.data = None
+    return msg

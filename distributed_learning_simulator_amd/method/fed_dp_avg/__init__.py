@@ -7,7 +7,6 @@ Byzantine clients can be injected as in `fed_trimmed_mean`."""
 
 from ...algorithm.dp_algorithm import DPFedAvgAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.robust_worker import ByzantineWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -15,7 +14,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_dp_avg",
     client_cls=ByzantineWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=DPFedAvgAlgorithm,
 )

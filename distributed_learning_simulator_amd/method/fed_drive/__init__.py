@@ -8,7 +8,6 @@ state; `true` uses the MSE-optimal scale with the error-feedback residual of `fe
 
 from ...algorithm.fed_avg_algorithm import FedAVGAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.error_feedback_worker import RotSignWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -16,7 +15,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_drive",
     client_cls=RotSignWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=FedAVGAlgorithm,
 )

@@ -5,7 +5,6 @@ Byzantine clients can be injected as in `fed_trimmed_mean`."""
 
 from ...algorithm.krum_algorithm import KrumAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.robust_worker import ByzantineWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -13,7 +12,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_krum",
     client_cls=ByzantineWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=KrumAlgorithm,
 )

@@ -6,7 +6,6 @@ byte counts are FedAvg's. Not in the reference."""
 
 from ...algorithm.fed_avg_algorithm import FedAVGAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.drift_worker import FedProxWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -14,7 +13,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_prox",
     client_cls=FedProxWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=FedAVGAlgorithm,
 )

@@ -7,7 +7,6 @@ no security to anybody."""
 
 from ...algorithm.secagg_algorithm import SecAggAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.secagg_worker import SecAggWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -15,7 +14,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_secagg",
     client_cls=SecAggWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=SecAggAlgorithm,
 )

@@ -7,7 +7,6 @@ client's rank, so the configs use full participation."""
 
 from ...algorithm.fed_avg_algorithm import FedAVGAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.error_feedback_worker import PackedTopKWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -15,7 +14,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_topk",
     client_cls=PackedTopKWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=FedAVGAlgorithm,
 )

@@ -6,7 +6,6 @@ worker can inject Byzantine clients (`worker/robust_worker.py`: `byzantine_numbe
 
 from ...algorithm.robust_algorithm import TrimmedMeanAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.robust_worker import ByzantineWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -14,7 +13,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_trimmed_mean",
     client_cls=ByzantineWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=TrimmedMeanAlgorithm,
 )

@@ -6,7 +6,6 @@ rule `yogi` from this method's name). Workers, uploads, aggregation and byte cou
 
 from ...algorithm.fed_avg_algorithm import FedAVGAlgorithm
 from ...server.aggregation_server import AggregationServer
-from ...topology.endpoints import ClientEndpoint, ServerEndpoint
 from ...worker.aggregation_worker import AggregationWorker
 from ..algorithm_factory import CentralizedAlgorithmFactory
 
@@ -14,7 +13,5 @@ CentralizedAlgorithmFactory.register_algorithm(
     algorithm_name="fed_yogi",
     client_cls=AggregationWorker,
     server_cls=AggregationServer,
-    client_endpoint_cls=ClientEndpoint,
-    server_endpoint_cls=ServerEndpoint,
     algorithm_cls=FedAVGAlgorithm,
 )

@@ -139,7 +139,7 @@ class ShapleyValueAlgorithm(FedAVGAlgorithm):
         self._rows.clear()
         msg = FlatParameterMessage(parameter=new, layout=self.layout, other_data=dict(self._other_data),
                                    end_training=bool(self._end_training))
-        self._reset_acc()
+        self._reset_round()
         return msg
 
     def clear_worker_data(self) -> None:

@@ -32,6 +32,8 @@ class Server(Executor):
 
     # reference server.py:123-131
     def _select_workers(self) -> list[int]:
+        # (not `config.clients_per_round`: an explicit 0 samples nobody here, where that rule
+        # reads 0 as unset)
         n = self.config.algorithm_kwargs.get("random_client_number")
         if n is None or int(n) >= self.worker_number:
             return list(range(self.worker_number))

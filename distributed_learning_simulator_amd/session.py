@@ -27,6 +27,7 @@ import time
 
 import torch
 
+from .config import clients_per_round
 from .data.datasets import create_dataset_collection, get_spec
 from .engine.memory import DEVICE_LOCK, plan_capacity
 from .engine.trainer import CohortTrainer, HyperParameter
@@ -112,8 +113,7 @@ class Session:
         self.practitioners = {p.worker_id: p for p in practitioners}
         self.model = build_model(cfg.model_name, self.dc.spec, cfg.model_kwargs)
         self.layout = self.model.layout
-        n_sel = int(cfg.algorithm_kwargs.get("random_client_number", cfg.worker_number) or cfg.worker_number)
-        n_sel = min(n_sel, cfg.worker_number)
+        n_sel = clients_per_round(cfg.algorithm_kwargs, cfg.worker_number)
         per_rank = math.ceil(n_sel / self.comm.world)
         if not cfg.optimizer_name:
             cfg.optimizer_name = "Adam" if self.dc.spec.kind == "graph" else "SGD"

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import torch
 
-from ..message import CohortMessage
+from ..message import CohortMessage, attach_payload
 from ..ops import compress, fl
 from ..utils.logging import get_logger
 
@@ -105,11 +105,8 @@ class ServerEndpoint:
 
 # ------------------------------------------------------------------ quantised
 def _attach(msg: CohortMessage, payload) -> CohortMessage:
-    """The upload becomes the packed payload: the dense rows are no longer part of the message
-    (kept only as the receiver's decode target)."""
-    msg.payload = payload
-    msg.extra["decode_into"] = msg.data
-    msg.data = None
+    """The upload becomes the packed payload (`message.attach_payload`), charged at its own bytes."""
+    attach_payload(msg, payload)
     msg.wire_bytes = payload.row_bytes()
     return msg
 

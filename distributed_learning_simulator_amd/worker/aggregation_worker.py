@@ -20,7 +20,7 @@ from typing import Iterator
 import torch
 
 from ..engine.hooks import ExecutorHookPoint
-from ..message import CohortMessage
+from ..message import CohortMessage, attach_payload
 from ..ops import fl
 from ..options import OPTIONS
 from .worker import Worker
@@ -153,3 +153,11 @@ class AggregationWorker(Worker):
             kind = "parameter"
         return CohortMessage(client_ids=list(wave), dataset_sizes=self.dataset_sizes(wave).to(rows.device),
                              kind=kind, data=data, layout=self.trainer.layout)
+
+    @staticmethod
+    def _attach_payload(msg: CohortMessage, payload, wire_bytes: list[int], decode_into: bool = True) -> CohortMessage:
+        """The wave's upload is a payload packed on the sender's side (`message.attach_payload`), which
+        states its own wire bytes per client (`ClientEndpoint._dense_wire`)."""
+        attach_payload(msg, payload, decode_into)
+        msg.extra["wire_bytes"] = wire_bytes
+        return msg

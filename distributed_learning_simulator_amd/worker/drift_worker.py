@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import torch
 
+from ..config import clients_per_round
 from ..message import CohortMessage
 from ..ops import fl
 from .aggregation_worker import AggregationWorker
@@ -54,10 +55,9 @@ class ScaffoldWorker(AggregationWorker):
         super().__init__(config, endpoint, session, **kwargs)
         _needs_broadcast_model(config, "fed_scaffold")
         assert self._send_parameter_diff
-        W = config.worker_number
-        sel = config.algorithm_kwargs.get("random_client_number", W) or W
+        sel = clients_per_round(config.algorithm_kwargs, config.worker_number)
         world = session.comm.world if session is not None else 1
-        if int(sel) < W and world > 1:
+        if sel < config.worker_number and world > 1:
             raise ValueError("fed_scaffold: partial participation (random_client_number < worker_number) with more "
                              "than one rank is refused: the client→rank assignment would not be stable, and a "
                              "client's control variate lives on the rank that trains it")

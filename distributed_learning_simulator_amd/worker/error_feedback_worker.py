@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import torch
 
+from ..config import clients_per_round
 from ..message import CohortMessage
 from ..ops import compress, fl
 from .aggregation_worker import AggregationWorker
@@ -29,6 +30,7 @@ class ErrorFeedbackWorker(AggregationWorker):
         super().__init__(config, endpoint, session, **kwargs)
         assert self._send_parameter_diff, "error feedback needs delta uploads"
         self._error: torch.Tensor | None = None  # [worker_number, P_pad] residuals
+        self._meta: compress.LayoutMeta | None = None  # (packed uploads: `_layout_meta`)
 
     def state_dict(self) -> dict:
         return {"error": self._error.cpu()} if self._error is not None else {}
@@ -44,7 +46,7 @@ class ErrorFeedbackWorker(AggregationWorker):
     def _ensure_error(self, P: int, device) -> torch.Tensor:
         if self._error is None:
             W = self.config.worker_number
-            sel = self.config.algorithm_kwargs.get("random_client_number", W) or W
+            sel = clients_per_round(self.config.algorithm_kwargs, W)
             world = self.session.comm.world if self.session is not None else 1
             assert sel >= W or world == 1, "error feedback residuals need a stable client→rank assignment"
             self._error = torch.zeros((W, P), dtype=torch.float32, device=device)
@@ -52,6 +54,25 @@ class ErrorFeedbackWorker(AggregationWorker):
 
     def _error_rows(self, wave: list[int], P: int, device) -> torch.Tensor:
         return self._ensure_error(P, device)[torch.tensor(wave, device=device)]
+
+    # ------------------------------------------------------------------ packed uploads
+    def _layout_meta(self, device) -> compress.LayoutMeta:
+        if self._meta is None or self._meta.seg_ids.device != device:
+            self._meta = compress.LayoutMeta.of(self.trainer.layout, device)
+        return self._meta
+
+    def _pack_with_residual(self, wave: list[int], rows: torch.Tensor, pack):
+        """`pack(rows, err)` over the wave's residual rows err [K, P], which it updates: in place when
+        the wave's clients are consecutive rows of `_error`, else gathered, packed and scattered back."""
+        K, P = rows.shape
+        error = self._ensure_error(P, rows.device)
+        if list(wave) == list(range(wave[0], wave[0] + K)):
+            return pack(rows, error[wave[0] : wave[0] + K])
+        idx = torch.tensor(wave, device=rows.device)
+        err = error[idx]
+        payload = pack(rows, err)
+        error[idx] = err
+        return payload
 
     def _get_sent_data(self, wave, theta_g, stats) -> CohortMessage:
         msg = super()._get_sent_data(wave, theta_g, stats)
@@ -89,32 +110,15 @@ class PackedTopKWorker(ErrorFeedbackWorker):
     def __init__(self, config, endpoint, session=None, **kwargs):
         super().__init__(config, endpoint, session, **kwargs)
         self.ratio = float(config.algorithm_kwargs.get("topk_ratio", 0.01))
-        self._meta: compress.LayoutMeta | None = None
 
     def topk(self) -> int:
         return max(1, int(self.trainer.layout.num_params * self.ratio))
 
     def _get_sent_data(self, wave, theta_g, stats) -> CohortMessage:
         msg = AggregationWorker._get_sent_data(self, wave, theta_g, stats)
-        rows = msg.data
-        K, P = rows.shape
-        if self._meta is None or self._meta.seg_ids.device != rows.device:
-            self._meta = compress.LayoutMeta.of(self.trainer.layout, rows.device)
-        error = self._ensure_error(P, rows.device)
-        if list(wave) == list(range(wave[0], wave[0] + K)):
-            payload = compress.pack_topk_ef(rows, error[wave[0] : wave[0] + K], self._meta, self.topk())
-        else:
-            idx = torch.tensor(wave, device=rows.device)
-            err = error[idx]
-            payload = compress.pack_topk_ef(rows, err, self._meta, self.topk())
-            error[idx] = err
-        # the upload is the packed payload (topology/endpoints._attach); the dense rows stay only
-        # as the receiver's decode target
-        msg.payload = payload
-        msg.extra["decode_into"] = rows
-        msg.data = None
-        msg.extra["wire_bytes"] = payload.row_bytes()
-        return msg
+        meta, k = self._layout_meta(msg.data.device), self.topk()
+        payload = self._pack_with_residual(wave, msg.data, lambda rows, err: compress.pack_topk_ef(rows, err, meta, k))
+        return self._attach_payload(msg, payload, payload.row_bytes())
 
 
 class RotSignWorker(ErrorFeedbackWorker):
@@ -130,28 +134,14 @@ class RotSignWorker(ErrorFeedbackWorker):
     def __init__(self, config, endpoint, session=None, **kwargs):
         super().__init__(config, endpoint, session, **kwargs)
         self.error_feedback = bool(config.algorithm_kwargs.get("error_feedback", False))
-        self._meta: compress.LayoutMeta | None = None
 
     def _get_sent_data(self, wave, theta_g, stats) -> CohortMessage:
         msg = AggregationWorker._get_sent_data(self, wave, theta_g, stats)
-        rows = msg.data
-        K, P = rows.shape
-        if self._meta is None or self._meta.seg_ids.device != rows.device:
-            self._meta = compress.LayoutMeta.of(self.trainer.layout, rows.device)
+        meta = self._layout_meta(msg.data.device)
         seeds = fl.row_seeds(self.upload_seed(self._round_num), list(wave))
-        if not self.error_feedback:
-            payload = compress.pack_rotsign(rows, self._meta, seeds, scale="unbiased")
+        if not self.error_feedback:  # (no residual: `_error` is never allocated)
+            payload = compress.pack_rotsign(msg.data, meta, seeds, scale="unbiased")
         else:
-            error = self._ensure_error(P, rows.device)
-            if list(wave) == list(range(wave[0], wave[0] + K)):
-                payload = compress.pack_rotsign_ef(rows, error[wave[0] : wave[0] + K], self._meta, seeds)
-            else:
-                idx = torch.tensor(wave, device=rows.device)
-                err = error[idx]
-                payload = compress.pack_rotsign_ef(rows, err, self._meta, seeds)
-                error[idx] = err
-        msg.payload = payload
-        msg.extra["decode_into"] = rows
-        msg.data = None
-        msg.extra["wire_bytes"] = payload.row_bytes()
-        return msg
+            payload = self._pack_with_residual(wave, msg.data,
+                                               lambda rows, err: compress.pack_rotsign_ef(rows, err, meta, seeds))
+        return self._attach_payload(msg, payload, payload.row_bytes())

@@ -42,8 +42,6 @@ class SecAggWorker(AggregationWorker):
         words, counters = fl.secagg_mask_rows(rows, proto.entry_table(wave), self.range, self.frac_bits,
                                               out=rows.view(torch.int32))
         wire = [proto.row_bytes(c, self.trainer.layout.num_params) for c in wave]
-        msg.payload = compress.MaskedPayload(words, wire)
-        msg.data = None
         msg.extra["secagg_stats"] = counters
-        msg.extra["wire_bytes"] = wire
-        return msg
+        # (no decode target: nobody can decode a masked upload)
+        return self._attach_payload(msg, compress.MaskedPayload(words, wire), wire, decode_into=False)
