@@ -3,6 +3,10 @@
 Importing this module on a machine with a GPU but without the built extension raises — the
 GPU path never silently falls back to PyTorch. Shape/stride contracts are asserted here
 before any launch (a mis-shaped launch on the box can fault the GPU).
+
+The wide conv / BatchNorm launches are keyword-only (the list is in csrc/bindings.cpp): the keys
+are the field / parameter names of csrc/dls.h, an optional operand that is off is left out, and
+the binding refuses a missing or unknown key before anything launches.
 """
 
 from __future__ import annotations
@@ -73,6 +77,18 @@ def _p(t) -> int:
         ring = _tls.keepalive = collections.deque(maxlen=48)  # > pointer args of any one launch
     ring.append(t)
     return t.data_ptr()
+
+
+def _i32(v, K: int | None = None):
+    """`v` as a contiguous int32 tensor (None stays None); with `K`, it holds one entry per client."""
+    v = None if v is None else v.to(torch.int32).contiguous()
+    assert v is None or K is None or v.shape == (K,), v.shape
+    return v
+
+
+def _pi32(v, K: int | None = None) -> int:
+    """Device pointer of _i32(v, K) (0 for None)."""
+    return _p(_i32(v, K))
 
 
 def _client_view(w: torch.Tensor, K: int):
@@ -217,12 +233,12 @@ def conv_fwd(x, w, stride: int, pad: int, bias=None, relu=False, out=None, stats
     BN partial sums Σy, Σy² over the rows of the first `stats_valid[k]` samples (bn_fwd(pre_stats=))."""
     K, B, H, W, C = x.shape
     Kw, Co, KH, KW, Ci = w.shape
-    OHs, OWs = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-    per_sample = max(H * W * (x.stride(-2) if x.dim() == 5 else C), OHs * OWs * Co) * x.element_size()
+    OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    per_sample = max(H * W * (x.stride(-2) if x.dim() == 5 else C), OH * OW * Co) * x.element_size()
     if B * per_sample >= WINDOW and stats is None and x_planes is None:
         chunks = _batch_chunks(B, per_sample)
         if out is None:
-            out = torch.empty((K, B, OHs, OWs, Co), dtype=x.dtype, device=x.device)
+            out = torch.empty((K, B, OH, OW, Co), dtype=x.dtype, device=x.device)
         for b0, b1 in chunks:
             conv_fwd(x[:, b0:b1], w, stride, pad, bias=bias, relu=relu, out=out[:, b0:b1], w_split=w_split)
         return out
@@ -232,8 +248,6 @@ def conv_fwd(x, w, stride: int, pad: int, bias=None, relu=False, out=None, stats
     _check(w, x.dtype, contiguous=False, name="w")
     assert Ci == C, (Ci, C)
     w_cs, rep = _client_view(w, K)
-    OH = (H + 2 * pad - KH) // stride + 1
-    OW = (W + 2 * pad - KW) // stride + 1
     if out is None:
         y, ldy = torch.empty((K, B, OH, OW, Co), dtype=x.dtype, device=x.device), Co
     else:
@@ -248,9 +262,6 @@ def conv_fwd(x, w, stride: int, pad: int, bias=None, relu=False, out=None, stats
     if stats is not None:
         assert f32 and stats.dtype == torch.float32 and stats.is_contiguous()
         assert stats.shape == (K, conv_stats_parts(M), 2, Co), stats.shape
-        if stats_valid is not None:
-            stats_valid = stats_valid.to(torch.int32).contiguous()
-            assert stats_valid.shape == (K,)
     if not f32 and ldx == C and ldy == Co and _gl(K, M, Co, C, KH * KW):
         _C.conv_gl_fwd(_p(x), _p(w), _p(y), _p(bias), B * H * W * C, M * Co, w_cs, b_cs, K, rep, B, H, W, C, OH, OW,
                        KH, KW, stride, pad, Co, int(relu), _s())
@@ -260,9 +271,11 @@ def conv_fwd(x, w, stride: int, pad: int, bias=None, relu=False, out=None, stats
     if x_planes is not None and ws_p and planes_ok(C, Co, ldx):
         xp, x_cs, x_lo = _planes_args(x_planes, x)  # LDS-DMA GEMM on pre-split operands
         planes_launches["fwd"] += 1
-    _C.conv_nt(xp, _p(w), _p(y), _p(bias), x_cs, y.stride(0), w_cs, b_cs, B, H, W, C, OH, OW, KH, KW, stride,
-               pad, 1, M, Co, KH * KW * Ci, rep, int(relu), K, 0, nt_f32_variant if f32 else nt_variant, NULL, NULL, f32,
-               _s(), ldx, ldy, _p(stats), _p(stats_valid), NULL, 0.0, 0.0, ws_p, ws_cs, ws_plane, x_lo, NULL, 0, 0)
+    _C.conv_nt(x=xp, w=_p(w), y=_p(y), bias=_p(bias), x_cs=x_cs, y_cs=y.stride(0), w_cs=w_cs, b_cs=b_cs, B=B, H=H, W=W,
+               C=C, OH=OH, OW=OW, KH=KH, KW=KW, stride=stride, pad=pad, dil=1, M=M, N=Co, R=KH * KW * Ci, rep=rep,
+               relu=int(relu), K=K, variant=nt_f32_variant if f32 else nt_variant, f32=f32, s=_s(), ldx=ldx, ldy=ldy,
+               stats=_p(stats), stats_valid=_pi32(stats_valid, K), wsplit=ws_p, ws_cs=ws_cs, ws_plane=ws_plane,
+               x_lo=x_lo)
     return y
 
 
@@ -321,7 +334,7 @@ def conv_dgrad(dy, w, in_hw, stride: int, pad: int, acc=None, w_split=None, dy_p
         assert stride > 1 and acc is not None and _f32(dy), "compact acc: fp32 strided dgrad only"
         assert acc.shape == (K, B, (H + stride - 1) // stride, (W + stride - 1) // stride, Ci), acc.shape
         assert acc.dtype == dy.dtype and acc.is_contiguous()
-    bnb_args = (NULL, NULL, 0, NULL, NULL, NULL, NULL, NULL)
+    opt = {}  # the optional operands that are on
     if bnb is not None:
         part, bx, bmask, bmean, brstd, bvalid, by = bnb
         R = B * H * W
@@ -336,7 +349,8 @@ def conv_dgrad(dy, w, in_hw, stride: int, pad: int, acc=None, w_split=None, dy_p
             assert by.dtype == F32 and by.is_contiguous() and by.numel() == K * R * Ci
         if bvalid is not None:
             assert bvalid.dtype == torch.int32 and bvalid.shape == (K,) and bvalid.is_contiguous()
-        bnb_args = (_p(part), _p(bx), bxld, _p(by), _p(bmask), _p(bmean), _p(brstd), _p(bvalid))
+        opt["bnb"] = dict(part=_p(part), x=_p(bx), xld=bxld, y=_p(by), mask=_p(bmask), mean=_p(bmean), rstd=_p(brstd),
+                          valid=_p(bvalid))
     if acc_mask is not None:
         assert acc is not None and not acc_compact and _f32(dy), "acc_mask: fp32 dgrad with a full-size acc"
         assert acc_mask.dtype == torch.uint8 and acc_mask.is_contiguous() and Ci % 8 == 0
@@ -386,12 +400,13 @@ def conv_dgrad(dy, w, in_hw, stride: int, pad: int, acc=None, w_split=None, dy_p
         if wt_buf is None:
             wt_buf = torch.empty(Kw * 2 * 9 * Ci * Co, dtype=BF16, device=dy.device)
         planes_launches["dgrad_wt"] += 1
+        opt.update(wt_buf=_p(wt_buf), wt_ready=int(wt_ready))
     else:
         assert not wt_ready, "conv_dgrad: a prebuilt wt_buf for a dgrad that does not take it"
-        wt_buf = None
-    _C.conv_dgrad(dyp, _p(w), _p(dx), _p(acc), w_cs, K, rep, B, OH, OW, Co, H, W, Ci, KH, KW, stride, pad,
-                  nt_f32_variant if f32 else nt_variant, f32, _s(), ld_dy, dy_cs, ws_p, ws_cs, ws_plane, dy_lo,
-                  int(bool(acc_compact)), *bnb_args, _p(wt_buf), _p(acc_mask), int(wt_ready))
+    _C.conv_dgrad(dy=dyp, w=_p(w), dx=_p(dx), acc=_p(acc), w_cs=w_cs, K=K, rep=rep, B=B, OH=OH, OW=OW, Co=Co, H=H, W=W,
+                  Ci=Ci, KH=KH, KW=KW, stride=stride, pad=pad, variant=nt_f32_variant if f32 else nt_variant, f32=f32,
+                  s=_s(), ld_dy=ld_dy, dy_cs=dy_cs, wsplit=ws_p, ws_cs=ws_cs, ws_plane=ws_plane, x_lo=dy_lo,
+                  acc_compact=int(bool(acc_compact)), acc_mask=_p(acc_mask), **opt)
     return dx
 
 
@@ -415,13 +430,22 @@ def _sgd_arg(sgd):
     f, _, off = sgd
     wd, mom, damp, nest = f.hyper
     assert f.theta.stride(1) == 1 and f.mom.stride(0) == f.theta.stride(0) and f.split.is_contiguous()
-    return (_p(f.theta) + off * 4, _p(f.mom) + off * 4, _p(f.split) + off * 2, f.theta.stride(0), f.split.stride(0),
-            f.split.stride(1), _p(f.lr), _p(f.active), _p(f.first), float(wd), float(mom), float(damp), int(nest))
+    return dict(theta=_p(f.theta) + off * 4, mom=_p(f.mom) + off * 4, split=_p(f.split) + off * 2,
+                th_cs=f.theta.stride(0), sp_cs=f.split.stride(0), sp_lo=f.split.stride(1), lr=_p(f.lr),
+                active=_p(f.active), first=_p(f.first), wd=float(wd), momentum=float(mom), dampening=float(damp),
+                nesterov=int(nest))
 
 
-def _tn_launch(dy, x, gw, dy_cs, x_cs, B, H, W, C, OH, OW, KH, KW, stride, pad, M, Co, R, K, f32, ldy, ldx,
-               dy_planes=None, x_planes=None, sgd=None):
-    """conv_tn with the split-K policy: slabs + ordered fold (fp32, deterministic) or atomics."""
+def _gemm_geom(rows: int, k: int) -> dict:
+    """A linear layer's [rows, k] GEMM as conv_nt / conv_tn geometry: a 1 x rows x 1 image, k channels, 1x1 filter."""
+    return dict(B=1, H=rows, W=1, C=k, OH=rows, OW=1, KH=1, KW=1, stride=1, pad=0, M=rows, R=k)
+
+
+def _tn_launch(dy, x, gw, dy_cs, x_cs, geom: dict, Co, K, f32, ldy, ldx, dy_planes=None, x_planes=None, sgd=None,
+               **bnb):
+    """conv_tn with the split-K policy: slabs + ordered fold (fp32, deterministic) or atomics.
+    `geom`: the B, H, W, C, OH, OW, KH, KW, stride, pad, M, R keys; `bnb`: the bnb_* keys, if any."""
+    M, C, R = geom["M"], geom["C"], geom["R"]
     planes = f32 and dy_planes is not None and x_planes is not None
     tv = (_C.conv_tn_pl_variant() if planes else tn_f32_variant) if f32 else tn_variant
     dyp, xp, dy_lo, x_lo = _p(dy), _p(x), 0, 0
@@ -438,8 +462,8 @@ def _tn_launch(dy, x, gw, dy_cs, x_cs, B, H, W, C, OH, OW, KH, KW, stride, pad, 
             gw.zero_()
     if sgd is not None:
         assert planes, "the SGD epilogue needs the plane TN kernels"
-    _C.conv_tn(dyp, xp, _p(gw), dy_cs, x_cs, gw.stride(0), B, H, W, C, OH, OW, KH, KW, stride, pad, M, Co, R, K, tv,
-               f32, _s(), ldy, ldx, part, dy_lo, x_lo, _sgd_arg(sgd))
+    _C.conv_tn(dy=dyp, x=xp, dw=_p(gw), dy_cs=dy_cs, x_cs=x_cs, dw_cs=gw.stride(0), Co=Co, K=K, variant=tv, f32=f32,
+               s=_s(), ldy=ldy, ldx=ldx, part=part, dy_lo=dy_lo, x_lo=x_lo, sgd=_sgd_arg(sgd), **geom, **bnb)
 
 
 def conv_wgrad_bn_bwd_ok(x_shape, Co: int, KH: int, KW: int, x_dtype=F32) -> bool:
@@ -465,33 +489,23 @@ def conv_wgrad(dy, x, gw, stride: int, pad: int, dy_planes=None, x_planes=None, 
     gives the shape."""
     K, B, OH, OW, Co = dy.shape
     _, _, H, W, C = x.shape
+    assert gw.dtype == torch.float32 and gw.shape[0] == K and gw[0].is_contiguous()
+    _, Co2, KH, KW, Ci = gw.shape
+    assert Co2 == Co and Ci == C
+    M = B * OH * OW
+    geom = dict(B=B, H=H, W=W, C=C, OH=OH, OW=OW, KH=KH, KW=KW, stride=stride, pad=pad, M=M, R=KH * KW * C)
     if bn_bwd is not None:
         dyo, xb, mk, cf, vr = bn_bwd
-        M = B * OH * OW
         assert dy_planes is None and x_planes is None and sgd is None and dy.dtype == F32 and x.dtype == F32
         assert max(M * Co, B * H * W * C) * 4 < WINDOW and x.is_contiguous()
-        assert conv_wgrad_bn_bwd_ok(x.shape, Co, gw.shape[2], gw.shape[3])
+        assert conv_wgrad_bn_bwd_ok(x.shape, Co, KH, KW)
         assert dyo.dtype == F32 and xb.dtype == F32 and dyo.is_contiguous() and xb.is_contiguous()
         assert dyo.numel() == K * M * Co and xb.numel() == K * M * Co
         assert cf.shape == (K, Co, 3) and cf.dtype == F32 and cf.is_contiguous(), cf.shape
         if mk is not None:
             assert mk.dtype == torch.uint8 and mk.is_contiguous() and mk.numel() == K * M * Co // 8
-        if vr is not None:
-            vr = vr.to(torch.int32).contiguous()
-            assert vr.shape == (K,)
-        assert gw.dtype == torch.float32 and gw.shape[0] == K and gw[0].is_contiguous()
-        _, Co2, KH, KW, Ci = gw.shape
-        assert Co2 == Co and Ci == C
-        R = KH * KW * C
-        splitk = _C.conv_tn_splitk(K, Co, R, M, C, tn_f32_variant, 1, Co, C, 0)
-        part = NULL
-        if splitk > 1:
-            if OPTIONS.deterministic:
-                part = _p(_tn_part(splitk * K * Co * R, gw.device))
-            else:
-                gw.zero_()
-        _C.conv_tn_bn_bwd(_p(dyo), _p(x), _p(gw), x.stride(0), gw.stride(0), B, H, W, C, OH, OW, KH, KW, stride, pad, M,
-                          Co, R, K, tn_f32_variant, _s(), C, part, _p(xb), _p(mk), _p(cf), _p(vr))
+        _tn_launch(dyo, x, gw, M * Co, x.stride(0), geom, Co, K, 1, Co, C, bnb_x=_p(xb), bnb_mask=_p(mk),
+                   bnb_coef=_p(cf), bnb_valid=_pi32(vr, K))
         return False
     per_sample = max(OH * OW * Co, H * W * C) * dy.element_size()
     if B * per_sample >= WINDOW and dy_planes is None:
@@ -507,16 +521,10 @@ def conv_wgrad(dy, x, gw, stride: int, pad: int, dy_planes=None, x_planes=None, 
     x, ldx = _pix_stride(x)
     f32 = _f32(dy)
     _check(x, dy.dtype, contiguous=False, name="x")
-    assert gw.dtype == torch.float32 and gw.shape[0] == K and gw[0].is_contiguous()
-    _, Co2, KH, KW, Ci = gw.shape
-    assert Co2 == Co and Ci == C
-    M = B * OH * OW
-    R = KH * KW * C
     use_pl = (dy_planes is not None and x_planes is not None and f32 and C % 8 == 0 and Co % 8 == 0
               and ldy == Co and ldx == C)
-    _tn_launch(dy, x, gw, dy.stride(0), x.stride(0), B, H, W, C, OH, OW, KH, KW, stride, pad, M, Co, R, K, f32,
-               ldy, ldx, dy_planes if use_pl else None, x_planes if use_pl else None,
-               sgd if use_pl else None)
+    _tn_launch(dy, x, gw, dy.stride(0), x.stride(0), geom, Co, K, f32, ldy, ldx, dy_planes if use_pl else None,
+               x_planes if use_pl else None, sgd if use_pl else None)
     return bool(use_pl and sgd is not None)
 
 
@@ -558,22 +566,17 @@ def halo_wgrad(dy, x, gw, dy_planes=None, x_planes=None, bn=None, valid=None, sg
         assert dxp.shape == (K, 2, R, N) and dxp.dtype == BF16 and dxp.is_contiguous(), dxp.shape
         if mk is not None:
             assert mk.dtype == torch.uint8 and mk.is_contiguous() and mk.numel() == K * R * N // 8
-        if vr is not None:
-            vr = vr.to(torch.int32).contiguous()
-            assert vr.shape == (K,)
-        bnb = (_p(xb), _p(mk), _p(cf), _p(vr), _p(dxp))
+        bnb = dict(bb_x=_p(xb), bb_mask=_p(mk), bb_coef=_p(cf), bb_valid=_pi32(vr, K), bb_dxp=_p(dxp))
         dyp, dy_cs, dy_lo, dm = _p(dyo), R * N, 0, 2
     elif dy_planes is not None:
-        dyp, dy_cs, dy_lo = _planes_args(dy_planes, dy)
-        dm = 0
+        (dyp, dy_cs, dy_lo), dm = _planes_args(dy_planes, dy), 0
     else:
         if not dy.is_contiguous():
             return False
         dyp, dy_cs, dy_lo, dm = _p(dy), dy.stride(0), 0, 1
-    coef, relu, valid_rows_p = NULL, 0, NULL
+    xbn = {}  # (x mode 2) the BatchNorm the x loader applies
     if x_planes is not None and bn is None:
-        xp, x_cs, x_lo = _planes_args(x_planes, x)
-        xm = 0
+        (xp, x_cs, x_lo), xm = _planes_args(x_planes, x), 0
     else:
         if not x.is_contiguous():
             return False
@@ -581,20 +584,12 @@ def halo_wgrad(dy, x, gw, dy_planes=None, x_planes=None, bn=None, valid=None, sg
         if bn is not None:
             c, r, v = bn
             assert c.shape == (K, C, 2) and c.dtype == F32 and c.is_contiguous(), c.shape
-            coef, relu, xm = _p(c), int(bool(r)), 2
-            if v is not None:
-                v = v.to(torch.int32).contiguous()
-                assert v.shape == (K,)
-                valid_rows_p = _p(v)
+            xbn, xm = dict(coef=_p(c), relu=int(bool(r)), x_valid=_pi32(v, K)), 2
     n = _C.halo_wgrad_part_floats(K, B, H, W, C, N)
     part = _p(_tn_part(n, dy.device)) if n else NULL
-    vimg = NULL
-    if valid is not None:
-        valid = valid.to(torch.int32).contiguous()
-        assert valid.shape == (K,)
-        vimg = _p(valid)
-    ok = _C.halo_wgrad(dyp, dy_cs, dy_lo, N, xp, x_cs, x_lo, C, coef, relu, valid_rows_p, _p(gw), gw.stride(0), part,
-                       K, B, H, W, C, N, xm, dm, _s(), vimg, _sgd_arg(sgd), bnb)
+    ok = _C.halo_wgrad(dy=dyp, dy_cs=dy_cs, dy_lo=dy_lo, ldy=N, x=xp, x_cs=x_cs, x_lo=x_lo, ldx=C, dw=_p(gw),
+                       dw_cs=gw.stride(0), part=part, K=K, B=B, H=H, W=W, C=C, N=N, xm=xm, dm=dm, s=_s(),
+                       valid_img=_pi32(valid, K), sgd=_sgd_arg(sgd), bnb=bnb, **xbn)
     if ok:
         planes_launches["wgrad_halo"] += 1
     return bool(ok)
@@ -620,10 +615,12 @@ def bias_grad(dy, gb):
 
 
 # --------------------------------------------------------------------------- linear
-def _out_planes(y):
-    """(pointer, client stride, hi→lo distance) of fresh [K, 2, ...] planes for an fp32 output y."""
+def _out_planes(y, on: bool):
+    """(fresh [K, 2, ...] planes for an fp32 output y, their conv_nt keys) — (None, {}) when off."""
+    if not on:
+        return None, {}
     yp = torch.empty((y.shape[0], 2) + tuple(y.shape[1:]), dtype=BF16, device=y.device)
-    return yp, _p(yp), yp.stride(0), yp.stride(1)
+    return yp, dict(yp=_p(yp), yp_cs=yp.stride(0), yp_lo=yp.stride(1))
 
 
 def linear_fwd(x, w, b=None, relu=False, acc=None, drop_p: float = 0.0, drop_seeds=None, w_split=None,
@@ -648,11 +645,11 @@ def linear_fwd(x, w, b=None, relu=False, acc=None, drop_p: float = 0.0, drop_see
     if x_planes is not None and f32 and ws_p and planes_ok(Fi, Fo):
         xp, x_cs, x_lo = _planes_args(x_planes.reshape((K, 2) + tuple(x.shape[1:])), x)
         planes_launches["linear_fwd"] += 1
-    yp, ypp, yp_cs, yp_lo = _out_planes(y) if (out_planes and f32) else (None, NULL, 0, 0)
-    _C.conv_nt(xp, _p(w), _p(y), _p(b), x_cs, N * Fo, w_cs, b_cs, 1, N, 1, Fi, N, 1, 1, 1, 1, 0, 1, N, Fo, Fi, rep,
-               int(relu), K, 0, nt_f32_variant if f32 else nt_variant, _p(acc), NULL, f32, _s(), 0, 0, NULL, NULL,
-               _p(_drop_seeds(drop_seeds, K, drop_p)), float(drop_p), 0.0, ws_p, ws_cs, ws_plane, x_lo,
-               ypp, yp_cs, yp_lo)
+    yp, yp_keys = _out_planes(y, out_planes and f32)
+    _C.conv_nt(x=xp, w=_p(w), y=_p(y), bias=_p(b), x_cs=x_cs, y_cs=N * Fo, w_cs=w_cs, b_cs=b_cs, dil=1, N=Fo, rep=rep,
+               relu=int(relu), K=K, variant=nt_f32_variant if f32 else nt_variant, acc=_p(acc), f32=f32, s=_s(),
+               drop_seeds=_p(_drop_seeds(drop_seeds, K, drop_p)), drop_p=float(drop_p), wsplit=ws_p, ws_cs=ws_cs,
+               ws_plane=ws_plane, x_lo=x_lo, **_gemm_geom(N, Fi), **yp_keys)
     return (y, yp) if out_planes else y
 
 
@@ -681,10 +678,11 @@ def linear_dgrad(dy, w, gate=None, gate_scale: float = 1.0, w_split=None, dy_pla
     if dy_planes is not None and f32 and ws_p and planes_ok(Fo, Fi):
         dyp, dy_cs, dy_lo = _planes_args(dy_planes.reshape((K, 2) + tuple(dy.shape[1:])), dy)
         planes_launches["linear_dgrad"] += 1
-    xp_, ypp, yp_cs, yp_lo = _out_planes(dx) if (out_planes and f32) else (None, NULL, 0, 0)
-    _C.conv_nt(dyp, _p(w), _p(dx), NULL, dy_cs, N * Fi, w_cs, 0, 1, N, 1, Fo, N, 1, 1, 1,
-               1, 0, 1, N, Fi, Fo, rep, 0, K, 1, nt_f32_variant if f32 else nt_variant, _p(acc), _p(gate), f32, _s(),
-               0, 0, NULL, NULL, NULL, 0.0, float(gate_scale), ws_p, ws_cs, ws_plane, dy_lo, ypp, yp_cs, yp_lo)
+    xp_, yp_keys = _out_planes(dx, out_planes and f32)
+    _C.conv_nt(x=dyp, w=_p(w), y=_p(dx), x_cs=dy_cs, y_cs=N * Fi, w_cs=w_cs, dil=1, N=Fi, rep=rep, K=K, b_kmajor=1,
+               variant=nt_f32_variant if f32 else nt_variant, acc=_p(acc), gate=_p(gate), f32=f32, s=_s(),
+               out_scale=float(gate_scale), wsplit=ws_p, ws_cs=ws_cs, ws_plane=ws_plane, x_lo=dy_lo,
+               **_gemm_geom(N, Fo), **yp_keys)
     return (dx, xp_) if out_planes else dx
 
 
@@ -706,11 +704,7 @@ def dropout_apply(x, seeds, p: float, planes: int = 0, colsum=None):
     x = x.contiguous()
     rows = x.numel() // (K * N)
     if planes and _f32(x) and N % 2 == 0:
-        if planes == 2:
-            out, yp = planes_buffer(tuple(x.shape), x.device)
-        else:
-            out = torch.empty_like(x)
-            yp = torch.empty((K, 2) + tuple(x.shape[1:]), dtype=BF16, device=x.device)
+        out, yp = _planes_out(tuple(x.shape), x.device, planes)
         cs_args = (NULL, 0, NULL)
         if colsum is not None:
             assert colsum.shape == (K, N) and colsum.dtype == F32 and colsum.stride(1) == 1
@@ -741,8 +735,7 @@ def linear_wgrad(dy, x, gw, gb=None, dy_planes=None, x_planes=None, sgd=None) ->
     use_pl = dy_planes is not None and x_planes is not None and f32 and Fi % 8 == 0 and Fo % 8 == 0
     dyp = dy_planes.reshape((K, 2) + tuple(dy.shape[1:])) if use_pl else None
     xp = x_planes.reshape((K, 2) + tuple(x.shape[1:])) if use_pl else None
-    _tn_launch(dy, x, gw, N * Fo, N * Fi, 1, N, 1, Fi, N, 1, 1, 1, 1, 0, N, Fo, Fi, K, f32, 0, 0, dyp, xp,
-               sgd if use_pl else None)
+    _tn_launch(dy, x, gw, N * Fo, N * Fi, _gemm_geom(N, Fi), Fo, K, f32, 0, 0, dyp, xp, sgd if use_pl else None)
     if gb is not None:
         _col_sum(dy, gb, K, N, Fo)
     return bool(use_pl and sgd is not None)
@@ -756,6 +749,24 @@ def planes_buffer(shape, device):
     buf = torch.empty(shape, dtype=F32, device=device)
     K = shape[0]
     return buf, buf.view(K, -1).view(BF16).view((K, 2) + tuple(shape[1:]))
+
+
+def _planes_out(shape, device, planes: int):
+    """(fp32 output, its [K, 2, *shape[1:]] split planes) of a producer's `planes` mode: 1 = the
+    kernel writes both, 2 = the planes only (the output is their fp32-typed alias, planes_buffer)."""
+    if planes == 2:
+        return planes_buffer(shape, device)
+    return (torch.empty(shape, dtype=F32, device=device),
+            torch.empty((shape[0], 2) + tuple(shape[1:]), dtype=BF16, device=device))
+
+
+def _pre_part(part, K: int, C: int) -> dict:
+    """bn_fwd's / bn_bwd's keys for [K, parts, 2, C] partials a GEMM epilogue wrote ({}: none)."""
+    if part is None:
+        return {}
+    assert part.dtype == torch.float32 and part.is_contiguous()
+    assert part.shape[0] == K and part.shape[2:] == (2, C), part.shape
+    return dict(pre_part=_p(part), pre_nparts=part.shape[1])
 
 
 def bn_fwd(x, gamma, beta, valid_rows=None, relu=False, residual=None, eps=1e-5, with_mask=False, pre_stats=None,
@@ -776,26 +787,16 @@ def bn_fwd(x, gamma, beta, valid_rows=None, relu=False, residual=None, eps=1e-5,
     x, ldx = _pix_stride(x)
     assert x.stride(0) == R * ldx, "client stride of a strided BN input must be R*ld"
     g_cs, rep = _client_view(gamma, K)
-    yp = None
     if planes and x.dtype == F32:
-        if planes == 2:
-            y, yp = planes_buffer((K, R, C), x.device)
-        else:
-            y = torch.empty((K, R, C), dtype=x.dtype, device=x.device)
-            yp = torch.empty((K, 2, R, C), dtype=BF16, device=x.device)
+        y, yp = _planes_out((K, R, C), x.device, planes)
     else:
         planes = 0
-        y = torch.empty((K, R, C), dtype=x.dtype, device=x.device)
-    mean = torch.empty((K, C), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((K, C), dtype=torch.float32, device=x.device)
+        y, yp = torch.empty((K, R, C), dtype=x.dtype, device=x.device), None
+    mean, rstd = (torch.empty((K, C), dtype=torch.float32, device=x.device) for _ in range(2))
     ws = _workspace(_C.bn_workspace_floats(K, R, C), x.device)
     if residual is not None:
         residual = residual.contiguous() if ldx == C else residual
         assert _pix_stride(residual)[1] == ldx and residual.stride() == x.stride()
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
-    if pre_stats is not None:
-        assert pre_stats.dtype == torch.float32 and pre_stats.is_contiguous()
-        assert pre_stats.shape[0] == K and pre_stats.shape[2:] == (2, C), pre_stats.shape
     mask = None
     if with_mask and relu and C % 8 == 0 and ldx % 8 == 0:
         mask = torch.empty((K, R, C // 8), dtype=torch.uint8, device=x.device)
@@ -803,10 +804,10 @@ def bn_fwd(x, gamma, beta, valid_rows=None, relu=False, residual=None, eps=1e-5,
     if res_coef is not None:
         assert residual is not None and x.dtype == F32 and res_coef.shape == (K, C, 2) and res_coef.is_contiguous()
     assert res_coef is not None or not res_relu, "res_relu needs res_coef"
-    _C.bn_fwd(_p(x), _p(gamma), _p(beta), _p(residual), _p(y), _p(mean), _p(rstd), _p(vr), g_cs, K, R, C, int(relu),
-              eps, rep, _p(ws), _p(mask), _f32(x), _s(), ldx, _p(pre_stats),
-              0 if pre_stats is None else pre_stats.shape[1], _p(yp), int(planes != 2), NULL, 1, _p(res_coef),
-              int(bool(res_relu)))
+    _C.bn_fwd(x=_p(x), gamma=_p(gamma), beta=_p(beta), res=_p(residual), y=_p(y), mean=_p(mean), rstd=_p(rstd),
+              valid_rows=_pi32(valid_rows), g_cs=g_cs, K=K, R=R, C=C, relu=int(relu), eps=eps, rep=rep, ws=_p(ws),
+              relu_mask=_p(mask), f32=_f32(x), s=_s(), ldx=ldx, yp=_p(yp), y_f32=int(planes != 2),
+              res_coef=_p(res_coef), res_relu=int(bool(res_relu)), **_pre_part(pre_stats, K, C))
     out = (y, mean, rstd, mask) if with_mask else (y, mean, rstd)
     return out + (yp,) if planes else out
 
@@ -820,17 +821,12 @@ def bn_coef(x, gamma, beta, valid_rows=None, eps=1e-5, pre_stats=None):
     x, ldx = _pix_stride(x)  # (a channel prefix of DenseNet's block buffer is read in place)
     assert x.stride(0) == R * ldx, "client stride of a strided BN input must be R*ld"
     g_cs, rep = _client_view(gamma, K)
-    mean = torch.empty((K, C), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((K, C), dtype=torch.float32, device=x.device)
+    mean, rstd = (torch.empty((K, C), dtype=torch.float32, device=x.device) for _ in range(2))
     coef = torch.empty((K, C, 2), dtype=torch.float32, device=x.device)
     ws = _workspace(_C.bn_workspace_floats(K, R, C), x.device)
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
-    if pre_stats is not None:
-        assert pre_stats.dtype == torch.float32 and pre_stats.is_contiguous()
-        assert pre_stats.shape[0] == K and pre_stats.shape[2:] == (2, C), pre_stats.shape
-    _C.bn_fwd(_p(x), _p(gamma), _p(beta), NULL, NULL, _p(mean), _p(rstd), _p(vr), g_cs, K, R, C, 0, eps, rep, _p(ws),
-              NULL, 1, _s(), ldx, _p(pre_stats),
-              0 if pre_stats is None else pre_stats.shape[1], NULL, 1, _p(coef), 0, NULL)
+    _C.bn_fwd(x=_p(x), gamma=_p(gamma), beta=_p(beta), mean=_p(mean), rstd=_p(rstd), valid_rows=_pi32(valid_rows),
+              g_cs=g_cs, K=K, R=R, C=C, eps=eps, rep=rep, ws=_p(ws), f32=1, s=_s(), ldx=ldx, coef_out=_p(coef), apply=0,
+              **_pre_part(pre_stats, K, C))
     return coef, mean, rstd
 
 
@@ -841,12 +837,10 @@ def bn_coef_sums(sums, C: int, gamma, beta, R: int, valid_rows=None, eps=1e-5):
     K = sums.shape[0]
     assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.shape[1] == 2 and C <= sums.shape[2]
     g_cs, rep = _client_view(gamma, K)
-    mean = torch.empty((K, C), dtype=torch.float32, device=sums.device)
-    rstd = torch.empty((K, C), dtype=torch.float32, device=sums.device)
+    mean, rstd = (torch.empty((K, C), dtype=torch.float32, device=sums.device) for _ in range(2))
     coef = torch.empty((K, C, 2), dtype=torch.float32, device=sums.device)
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
-    _C.bn_coef_sums(_p(sums), sums.stride(0), sums.shape[2], _p(gamma), _p(beta), _p(vr), g_cs, K, R, C, eps, rep,
-                    _p(mean), _p(rstd), _p(coef), _s())
+    _C.bn_coef_sums(_p(sums), sums.stride(0), sums.shape[2], _p(gamma), _p(beta), _pi32(valid_rows), g_cs, K, R, C, eps,
+                    rep, _p(mean), _p(rstd), _p(coef), _s())
     return coef, mean, rstd
 
 
@@ -869,9 +863,9 @@ def chan_sums_f64(x, valid_rows, out):
     x, ldx = _pix_stride(x)
     assert x.dtype == F32 and x.stride(0) == R * ldx and 2 * C <= 1024
     assert out.dtype == torch.float64 and out.shape == (K, 2, C) and out.stride(2) == 1
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
     ws = torch.empty(max(1, K * _C.chan_sums_f64_ws(R, C)), dtype=torch.float64, device=x.device)
-    _C.chan_sums_f64(_p(x), x.stride(0), ldx, K, R, C, _p(vr), _p(ws), _p(out), out.stride(0), out.stride(1), _s())
+    _C.chan_sums_f64(_p(x), x.stride(0), ldx, K, R, C, _pi32(valid_rows), _p(ws), _p(out), out.stride(0), out.stride(1),
+                     _s())
 
 
 def halo_bn_ok(shape, w) -> bool:
@@ -890,8 +884,7 @@ def bn_apply_only(x, coef, valid_rows, relu: bool, yp, mask=None, y=None):
     assert y is None or (y.shape == (K, R, C) and y.dtype == F32 and y.is_contiguous())
     if mask is not None:
         assert mask.shape == (K, R, C // 8) and C % 8 == 0
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
-    _C.bn_apply_only(_p(x), _p(coef), _p(vr), K, R, C, int(relu), _p(yp), _p(mask), _s(), _p(y))
+    _C.bn_apply_only(_p(x), _p(coef), _pi32(valid_rows), K, R, C, int(relu), _p(yp), _p(mask), _s(), _p(y))
 
 
 def conv_halo_bn_fwd(x, coef, relu: bool, valid_rows, w, w_split, stats=None, stats_valid=None, yp=None, mask=None):
@@ -909,17 +902,16 @@ def conv_halo_bn_fwd(x, coef, relu: bool, valid_rows, w, w_split, stats=None, st
     w_cs, rep = _client_view(w, K)
     ws_p, ws_cs, ws_plane = _wsplit_args(w_split, w)
     y = torch.empty((K, B, H, W, N), dtype=F32, device=x.device)
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
     if stats is not None:
         assert stats.shape == (K, conv_stats_parts(B * H * W), 2, N) and stats.is_contiguous()
-        if stats_valid is not None:
-            stats_valid = stats_valid.to(torch.int32).contiguous()
     if yp is not None:
         assert yp.shape == (K, 2, B * H * W, C) and yp.dtype == BF16 and yp.is_contiguous()
     if mask is not None:
         assert mask.shape == (K, B * H * W, C // 8) and mask.dtype == torch.uint8 and mask.is_contiguous()
-    ok = _C.conv_halo_bn_fwd(_p(x), x.stride(0), _p(coef), int(relu), _p(vr), ws_p, ws_cs, ws_plane, rep, _p(y),
-                             y.stride(0), K, B, H, W, C, N, _p(stats), _p(stats_valid), _s(), _p(yp), _p(mask))
+    ok = _C.conv_halo_bn_fwd(
+        x=_p(x), x_cs=x.stride(0), coef=_p(coef), relu=int(relu), valid_rows=_pi32(valid_rows), wsplit=ws_p,
+        ws_cs=ws_cs, ws_plane=ws_plane, rep=rep, y=_p(y), y_cs=y.stride(0), K=K, B=B, H=H, W=W, C=C, N=N, stats=_p(stats),
+        stats_valid=_pi32(stats_valid), s=_s(), yp=_p(yp), mask=_p(mask))
     if ok:
         planes_launches["fwd_bn_fused"] += 1
     return y if ok else None
@@ -956,11 +948,11 @@ def dense_wgrad(dy, y, gw, x=None, bn_coef=None, valid_rows=None) -> bool:
     if d.data_ptr() != dy.data_ptr() or ldy % 4 or dy.stride(0) != B * H * W * ldy:
         return False
     assert gw.shape == (K, N, 3, 3, C) and gw.dtype == F32 and gw[0].is_contiguous(), gw.shape
-    vr = valid_rows.to(torch.int32).contiguous() if (valid_rows is not None and bn_coef is not None) else None
     n = _C.dense_wgrad_part_floats(K, B, H, W, C)
     part = _grown(_dw_part_cache, (dy.device, torch.cuda.current_stream().cuda_stream), n, dy.device)
-    ok = _C.dense_wgrad(_p(d), dy.stride(0), ldy, _p(src), src_cs, _p(gw), gw.stride(0), _p(part), K, B, H, W, C, N,
-                        _s(), _p(bn_coef), ldx, _p(vr))
+    ok = _C.dense_wgrad(dy=_p(d), dy_cs=dy.stride(0), ldy=ldy, y=_p(src), y_cs=src_cs, dw=_p(gw), dw_cs=gw.stride(0),
+                        part=_p(part), K=K, B=B, H=H, W=W, C=C, N=N, s=_s(), bn_sc=_p(bn_coef), ldy_x=ldx,
+                        valid_rows=_pi32(valid_rows if bn_coef is not None else None))
     if ok:
         planes_launches["wgrad_dense_halo"] += 1
     return bool(ok)
@@ -1009,12 +1001,12 @@ def dense_dgrad_bn(dy, w, x, dx, y, mask, mean, rstd, gamma, valid_rows, ggamma,
     if bn_coef is not None:
         assert bn_coef.shape == (K, C, 2) and bn_coef.dtype == F32 and bn_coef.is_contiguous()
         y = mask = None
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
     dg_cs = ggamma.stride(0) if ggamma is not None else 0
     ws = _workspace(_C.dense_dgrad_ws_floats(K, B, H, C), dy.device)
-    ok = _C.dense_dgrad_bn(_p(d), dy.stride(0), ldy, _p(w), w_cs, rep, _p(x), _p(dx), x.stride(0), ldx, _p(mask),
-                           _p(y), _p(mean), _p(rstd), _p(vr), _p(gamma), g_cs, _p(ggamma), _p(gbeta), dg_cs, _p(ws), K,
-                           B, H, W, C, N, _s(), _p(bn_coef))
+    ok = _C.dense_dgrad_bn(dy=_p(d), dy_cs=dy.stride(0), ldy=ldy, w=_p(w), w_cs=w_cs, rep=rep, x=_p(x), dx=_p(dx),
+                           x_cs=x.stride(0), ldx=ldx, mask=_p(mask), y=_p(y), mean=_p(mean), rstd=_p(rstd),
+                           valid_rows=_pi32(valid_rows), gamma=_p(gamma), g_cs=g_cs, dgamma=_p(ggamma), dbeta=_p(gbeta),
+                           dg_cs=dg_cs, ws=_p(ws), K=K, B=B, H=H, W=W, C=C, N=N, s=_s(), bn_sc=_p(bn_coef))
     if ok:
         planes_launches["dgrad_dense_bn"] += 1
     return bool(ok)
@@ -1073,20 +1065,18 @@ def conv_halo_bn_dense_fwd(x, coef, relu: bool, valid_rows, w, out, w_planes=Non
         w_planes = dense_weight_planes(w)
     assert w_planes.shape == (Kw, 2, N, 3, 3, C32) and w_planes.dtype == BF16 and w_planes.is_contiguous()
     rep = K // Kw
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
     if stats is not None:
         assert stats.shape == (K, conv_stats_parts(B * H * W), 2, N) and stats.is_contiguous()
-        if stats_valid is not None:
-            stats_valid = stats_valid.to(torch.int32).contiguous()
     if ny is not None:
         assert ny.shape == (K, B * H * W, C) and ny.dtype == F32 and ny.is_contiguous()
     if mask is not None:
         assert ny is not None and C % 8 == 0 and mask.shape == (K, B * H * W, C // 8) and mask.dtype == torch.uint8
         assert mask.is_contiguous()
-    ok = _C.conv_halo_bn_dense_fwd(_p(xs), xs.stride(0), ldx, C, _p(cp), int(relu), _p(vr), _p(w_planes),
-                                   w_planes.stride(0) if Kw > 1 else 0, w_planes.stride(1), rep, _p(y), y.stride(0),
-                                   ldy, K, B, H, W, C32, N, _p(stats), _p(stats_valid), _p(ny),
-                                   ny.stride(0) if ny is not None else 0, C, _p(mask), _s())
+    ok = _C.conv_halo_bn_dense_fwd(
+        x=_p(xs), x_cs=xs.stride(0), ldx=ldx, creal=C, coef=_p(cp), relu=int(relu), valid_rows=_pi32(valid_rows),
+        wsplit=_p(w_planes), ws_cs=w_planes.stride(0) if Kw > 1 else 0, ws_plane=w_planes.stride(1), rep=rep, y=_p(y),
+        y_cs=y.stride(0), ldy=ldy, K=K, B=B, H=H, W=W, C=C32, N=N, stats=_p(stats), stats_valid=_pi32(stats_valid),
+        ny=_p(ny), ny_cs=ny.stride(0) if ny is not None else 0, ldny=C, mask=_p(mask), s=_s())
     if ok:
         planes_launches["fwd_bn_dense"] += 1
     return bool(ok)
@@ -1116,18 +1106,13 @@ def bn_bwd(dy, x, y, mean, rstd, gamma, valid_rows, relu, ggamma, gbeta, need_dp
         assert ldx == C, "strided x needs a strided dx_out"
     dxp = None
     if dx_planes and dx_out is None and x.dtype == F32:
-        if dx_planes == 2:
-            dx, dxp = planes_buffer((K, R, C), x.device)
-        else:
-            dx = torch.empty((K, R, C), dtype=x.dtype, device=x.device)
-            dxp = torch.empty((K, 2, R, C), dtype=BF16, device=x.device)
+        dx, dxp = _planes_out((K, R, C), x.device, dx_planes)
     else:
         dx_planes = 0
         if dx_out is None:
             dx = torch.empty((K, R, C), dtype=x.dtype, device=x.device)
     dpre = torch.empty((K, R, C), dtype=x.dtype, device=x.device) if need_dpre else None
     ws = _workspace(_C.bn_workspace_floats(K, R, C), x.device)
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
     dg_cs = ggamma.stride(0) if ggamma is not None else 0
     assert dy.dtype == x.dtype == gamma.dtype
     if pre_part is not None:
@@ -1135,10 +1120,11 @@ def bn_bwd(dy, x, y, mean, rstd, gamma, valid_rows, relu, ggamma, gbeta, need_dp
     if coef_out is not None:
         assert coef_out.shape == (K, C, 3) and coef_out.dtype == F32 and coef_out.is_contiguous()
         assert dx_out is None and not need_dpre
-    _C.bn_bwd(_p(dy), _p(x), _p(y), _p(mean), _p(rstd), _p(gamma), _p(vr), g_cs, K, R, C, int(relu), _p(dx), _p(dpre),
-              _p(ggamma), _p(gbeta), dg_cs, _p(ws), _p(relu_mask), _f32(x), _s(), ldx,
-              int(dx_out is not None), _p(dxp), int(dx_planes != 2), _p(pre_part),
-              0 if pre_part is None else pre_part.shape[1], _p(coef_out), 1 if coef_out is not None else 0)
+    _C.bn_bwd(dy=_p(dy), x=_p(x), y=_p(y), mean=_p(mean), rstd=_p(rstd), gamma=_p(gamma), valid_rows=_pi32(valid_rows),
+              g_cs=g_cs, K=K, R=R, C=C, relu=int(relu), dx=_p(dx), dpre=_p(dpre), dgamma=_p(ggamma), dbeta=_p(gbeta),
+              dg_cs=dg_cs, ws=_p(ws), relu_mask=_p(relu_mask), f32=_f32(x), s=_s(), ldx=ldx, dxp=_p(dxp),
+              acc_dx=int(dx_out is not None), dx_f32=int(dx_planes != 2), coef_ext=_p(coef_out),
+              stage=1 if coef_out is not None else 0, **_pre_part(pre_part, K, C))
     if coef_out is not None:
         return None
     if dx_planes:
@@ -1151,23 +1137,24 @@ def bn_bwd_apply_planes(dy, x, relu_mask, coef, valid_rows, dxp) -> None:
     planes into `dxp` [K, 2, R, C] (dy, x [K, R, C] fp32 contiguous; `relu_mask` the ReLU bits or
     None for no gate) — bn_bwd's own apply pass, for a consumer that cannot apply it itself."""
     K, R, C = x.shape
-    assert dy.shape == x.shape and dy.is_contiguous() and x.is_contiguous() and dy.dtype == F32 == x.dtype
-    assert coef.shape == (K, C, 3) and dxp.shape == (K, 2, R, C) and dxp.is_contiguous()
-    ws = _workspace(_C.bn_workspace_floats(K, R, C), x.device)
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
-    _C.bn_bwd(_p(dy), _p(x), NULL, NULL, NULL, NULL, _p(vr), 0, K, R, C, int(relu_mask is not None), _p(dxp), NULL,
-              NULL, NULL, 0, _p(ws), _p(relu_mask), 1, _s(), C, 0, _p(dxp), 0, NULL, 0, _p(coef), 2)
+    assert dxp.shape == (K, 2, R, C) and dxp.is_contiguous()
+    _bn_bwd_apply(dy, x, relu_mask, coef, valid_rows, dx=_p(dxp), dxp=_p(dxp), dx_f32=0)
 
 
 def bn_bwd_apply_f32(dy, x, relu_mask, coef, valid_rows, dx) -> None:
     """bn_bwd_apply_planes with the fp32 dX as the output: `dx` [K, R, C] fp32 contiguous."""
+    assert dx.shape == x.shape and dx.dtype == F32 and dx.is_contiguous()
+    _bn_bwd_apply(dy, x, relu_mask, coef, valid_rows, dx=_p(dx))
+
+
+def _bn_bwd_apply(dy, x, relu_mask, coef, valid_rows, **out) -> None:
+    """bn_bwd's stage 2 (apply only) into `out`: the dx (+ dxp, dx_f32) keys of the launch."""
     K, R, C = x.shape
     assert dy.shape == x.shape and dy.is_contiguous() and x.is_contiguous() and dy.dtype == F32 == x.dtype
-    assert coef.shape == (K, C, 3) and dx.shape == (K, R, C) and dx.dtype == F32 and dx.is_contiguous()
+    assert coef.shape == (K, C, 3)
     ws = _workspace(_C.bn_workspace_floats(K, R, C), x.device)
-    vr = valid_rows.to(torch.int32).contiguous() if valid_rows is not None else None
-    _C.bn_bwd(_p(dy), _p(x), NULL, NULL, NULL, NULL, _p(vr), 0, K, R, C, int(relu_mask is not None), _p(dx), NULL,
-              NULL, NULL, 0, _p(ws), _p(relu_mask), 1, _s(), C, 0, NULL, 1, NULL, 0, _p(coef), 2)
+    _C.bn_bwd(dy=_p(dy), x=_p(x), valid_rows=_pi32(valid_rows), K=K, R=R, C=C, relu=int(relu_mask is not None),
+              ws=_p(ws), relu_mask=_p(relu_mask), f32=1, s=_s(), ldx=C, coef_ext=_p(coef), stage=2, **out)
 
 
 # ------------------------------------------------------------------------ layernorm
@@ -1225,7 +1212,7 @@ def _gn_valid(valid, K: int):
     if valid is None:
         return None
     assert valid.shape == (K,) and valid.is_cuda
-    return valid.to(torch.int32).contiguous()
+    return _i32(valid)
 
 
 def gn_workspace_floats(K: int, B: int, C: int) -> int:
@@ -1339,8 +1326,8 @@ def gap_bwd(dy, x_shape):
 def ce_fwd_bwd(logits, labels, valid=None):
     K, B, NC = logits.shape
     logits = logits.contiguous()
-    lab = labels.to(torch.int32).contiguous()
-    v = valid.to(torch.int32).contiguous() if valid is not None else None
+    lab = _i32(labels)
+    v = _i32(valid)
     loss = torch.empty(K, dtype=torch.float32, device=logits.device)
     correct = torch.empty(K, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
@@ -1354,7 +1341,7 @@ def ce_fwd_bwd(logits, labels, valid=None):
 def embedding_fwd(tokens, table, scale: float = 1.0, pe=None):
     """table[tokens] · scale (+ pe[position]) in one pass; pe [L, D] fp32 (L = tokens.shape[-1])."""
     K = tokens.shape[0]
-    tok = tokens.to(torch.int32).contiguous()
+    tok = _i32(tokens)
     t_cs, rep = _client_view(table, K)
     D = table.shape[-1]
     n_tok = tok.numel() // K
@@ -1369,7 +1356,7 @@ def embedding_fwd(tokens, table, scale: float = 1.0, pe=None):
 
 def embedding_bwd(dy, tokens, gtable, scale: float = 1.0):
     K = tokens.shape[0]
-    tok = tokens.to(torch.int32).contiguous()
+    tok = _i32(tokens)
     D = dy.shape[-1]
     gtable.zero_()
     if OPTIONS.deterministic:
@@ -1381,7 +1368,7 @@ def embedding_bwd(dy, tokens, gtable, scale: float = 1.0):
         sk, order = torch.sort(keys, stable=True)
         n = keys.numel()
         part = torch.empty(_C.embedding_bwd_part_floats(n, D), dtype=torch.float32, device=dy.device)
-        _C.embedding_bwd_sorted(_p(sk.contiguous()), _p(order.to(torch.int32).contiguous()), _p(dy.contiguous()),
+        _C.embedding_bwd_sorted(_p(sk.contiguous()), _pi32(order), _p(dy.contiguous()),
                                 _p(gtable), n, D, V, gtable.stride(0), _f32(dy), _s(), float(scale), _p(part))
         return
     _C.embedding_bwd(_p(tok), _p(dy.contiguous()), _p(gtable), K, tok.numel() // K, D, gtable.stride(0), _f32(dy), _s(),
@@ -1655,8 +1642,8 @@ def spmm(rowptr, col, val, x):
     K, Nx, F = x.shape
     N = rowptr.numel() - 1
     y = torch.empty((K, N, F), dtype=x.dtype, device=x.device)
-    rp = rowptr.to(torch.int32).contiguous()
-    cl = col.to(torch.int32).contiguous()
+    rp = _i32(rowptr)
+    cl = _i32(col)
     vl = val.to(torch.float32).contiguous()
     _C.spmm(_p(rp), _p(cl), _p(vl), _p(x), _p(y), K, N, Nx, F, Nx * F, N * F, f32, _s())
     return y
@@ -2046,7 +2033,7 @@ def block_sq_norms(x, block_offsets, block_ids):
     K, P, ld = _row_args(x)
     nb = int(block_offsets.numel()) - 1
     out = torch.empty((K, nb), dtype=torch.float32, device=x.device)
-    _C.block_sq_norms(_p(x), _p(block_ids.to(torch.int32).contiguous()), _p(out), K, P, ld, nb, _s())
+    _C.block_sq_norms(_p(x), _pi32(block_ids), _p(out), K, P, ld, nb, _s())
     return out
 
 
@@ -2055,7 +2042,7 @@ def stochastic_qdq(x, seg_ids, nseg, seeds, levels):
     assert len(seeds) == K
     mn = torch.full((K, nseg), float("inf"), dtype=torch.float32, device=x.device)
     mx = torch.full((K, nseg), float("-inf"), dtype=torch.float32, device=x.device)
-    seg = seg_ids.to(torch.int32).contiguous()
+    seg = _i32(seg_ids)
     out = x.contiguous().clone()
     ld = out.stride(0)
     sd = _seeds_dev(seeds)
@@ -2075,7 +2062,7 @@ def seg_minmax(x, seg_ids, nseg):
     K, P, ld = _row_args(x)
     mn = torch.full((K, nseg), float("inf"), dtype=torch.float32, device=x.device)
     mx = torch.full((K, nseg), float("-inf"), dtype=torch.float32, device=x.device)
-    _C.seg_minmax(_p(x), _p(seg_ids.to(torch.int32).contiguous()), _p(mn), _p(mx), K, P, ld, nseg, _s())
+    _C.seg_minmax(_p(x), _pi32(seg_ids), _p(mn), _p(mx), K, P, ld, nseg, _s())
     return mn, mx
 
 
@@ -2083,7 +2070,7 @@ def seg_sq_sums(x, seg_ids, nseg):
     """Σx² per (row, segment); segments are 16-element aligned layout tensors."""
     K, P, ld = _row_args(x)
     out = torch.empty((K, nseg), dtype=torch.float32, device=x.device)
-    _C.block_sq_norms(_p(x), _p(seg_ids.to(torch.int32).contiguous()), _p(out), K, P, ld, nseg, _s())
+    _C.block_sq_norms(_p(x), _pi32(seg_ids), _p(out), K, P, ld, nseg, _s())
     return out
 
 
@@ -2091,7 +2078,7 @@ def nnadq_qdq(x, seg_ids, lo, scale, levels):
     K, P, ld = _row_args(x)
     out = x.contiguous().clone()
     nseg = lo.shape[1]
-    _C.nnadq_qdq(_p(out), _p(seg_ids.to(torch.int32).contiguous()), _p(lo.contiguous()), _p(scale.contiguous()),
+    _C.nnadq_qdq(_p(out), _pi32(seg_ids), _p(lo.contiguous()), _p(scale.contiguous()),
                  _p(levels.float().contiguous()), K, P, out.stride(0), nseg, _s())
     return out
 
@@ -2115,7 +2102,7 @@ def gather_rows(src, idx):
     """src [N, ...] contiguous (rows a multiple of 16 B), idx int -> [len(idx), ...]"""
     row_bytes = src[0].numel() * src.element_size()
     assert row_bytes % 16 == 0 and src.is_contiguous()
-    i32 = idx.reshape(-1).to(torch.int32).contiguous()
+    i32 = _i32(idx.reshape(-1))
     out = torch.empty((i32.numel(), *src.shape[1:]), dtype=src.dtype, device=src.device)
     _C.gather_rows(_p(src), _p(i32), _p(out), i32.numel(), row_bytes, _s())
     return out

@@ -94,18 +94,19 @@ def test_conv_f32_every_variant(hip, case):
     M = B * OH * ((W + 2 * p - k) // s + 1)
     for v in range(hip._C.conv_nt_f32_num_variants()):
         y = torch.empty_like(dy)
-        hip._C.conv_nt(x.data_ptr(), w.data_ptr(), y.data_ptr(), 0, B * H * W * Ci, M * Co, w.stride(0), 0, B, H, W,
-                       Ci, OH, y.shape[3], k, k, s, p, 1, M, Co, k * k * Ci, 1, 0, K, 0, v, 0, 0, 1, stream, 0, 0, 0, 0, 0, 0.0, 0.0,
-                       0, 0, 0, 0, 0, 0, 0)
+        hip._C.conv_nt(x=x.data_ptr(), w=w.data_ptr(), y=y.data_ptr(), x_cs=B * H * W * Ci, y_cs=M * Co, w_cs=w.stride(0),
+                       B=B, H=H, W=W, C=Ci, OH=OH, OW=y.shape[3], KH=k, KW=k, stride=s, pad=p, dil=1, M=M, N=Co,
+                       R=k * k * Ci, rep=1, K=K, variant=v, f32=1, s=stream)
         _close(y, y_ref)
         dx = torch.empty_like(x)
-        hip._C.conv_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0, w.stride(0), K, 1, B, OH, y.shape[3], Co, H,
-                          W, Ci, k, k, s, p, v, 1, stream, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+        hip._C.conv_dgrad(dy=dy.data_ptr(), w=w.data_ptr(), dx=dx.data_ptr(), w_cs=w.stride(0), K=K, rep=1, B=B, OH=OH,
+                          OW=y.shape[3], Co=Co, H=H, W=W, Ci=Ci, KH=k, KW=k, stride=s, pad=p, variant=v, f32=1, s=stream)
         _close(dx, dx_ref)
     for v in range(hip._C.conv_tn_f32_num_variants()):
         gw = torch.zeros((K, Co, k, k, Ci), device=DEV)
-        hip._C.conv_tn(dy.data_ptr(), x.data_ptr(), gw.data_ptr(), M * Co, B * H * W * Ci, gw.stride(0), B, H, W, Ci,
-                       OH, dy.shape[3], k, k, s, p, M, Co, k * k * Ci, K, v, 1, stream, 0, 0, 0, 0, 0, None)
+        hip._C.conv_tn(dy=dy.data_ptr(), x=x.data_ptr(), dw=gw.data_ptr(), dy_cs=M * Co, x_cs=B * H * W * Ci,
+                       dw_cs=gw.stride(0), B=B, H=H, W=W, C=Ci, OH=OH, OW=dy.shape[3], KH=k, KW=k, stride=s, pad=p, M=M,
+                       Co=Co, R=k * k * Ci, K=K, variant=v, f32=1, s=stream)
         _close(gw, dw_ref)
 
 
@@ -1343,6 +1344,53 @@ def test_dgrad_transposed_weight_planes(hip, case):
     _close(out, km, 2e-5)
     again = hip.conv_dgrad(dy, w, (H, H), 1, 1, w_split=ws, dy_planes=dyp, acc=acc, wt=True)
     assert torch.equal(again, out)
+
+
+def test_dgrad_prebuilt_weight_planes(hip):
+    """conv_dgrad(wt_buf=dgrad_wt_prebuild(...)): the transposed weight planes built ahead of the
+    dgrad (a training step builds them before the SGD epilogue rewrites the weight planes) give
+    bitwise the wt=True dgrad that builds them itself, within 1e-5 of the fp64 oracle — at the
+    smallest shape the path accepts (8 x 8, 32 channels)."""
+    K, B, H, C, Co = 2, 2, 8, 32, 32
+    torch.manual_seed(23)
+    dy = _f(K, B, H, H, Co)
+    w = _f(K, Co, 3, 3, C, scale=0.1)
+    n = Co * 9 * C
+    wpl = torch.empty((K, 2, n), dtype=torch.bfloat16, device=DEV)
+    hip.split_rows(w.reshape(K, n).contiguous(), wpl)
+    ws = wpl[:, 0].unflatten(1, (Co, 3, 3, C))
+    dyp = hip.split_planes(dy)
+    acc = _f(K, B, H, H, C)
+    own = hip.conv_dgrad(dy, w, (H, H), 1, 1, w_split=ws, dy_planes=dyp, acc=acc, wt=True)
+    wt_buf = hip.dgrad_wt_prebuild(dy.shape, w, ws, (H, H), 1, 1)
+    assert wt_buf is not None
+    before = hip.planes_launches["dgrad_wt"]
+    out = hip.conv_dgrad(dy, w, (H, H), 1, 1, w_split=ws, dy_planes=dyp, acc=acc, wt_buf=wt_buf)
+    assert hip.planes_launches["dgrad_wt"] == before + 1
+    assert torch.equal(out, own)
+    _close(out, ref.conv_dgrad(_d(dy), _d(w), (H, H), 1, 1) + _d(acc))
+
+
+def test_bn_bwd_apply_f32(hip):
+    """bn_bwd(coef_out=) then bn_bwd_apply_f32 (the two stages apart, fp32 dX out) write bitwise the
+    dX of one plain bn_bwd: a row count that is no multiple of 32, ragged valid rows, a ReLU mask."""
+    K, R, C = 2, 40, 8
+    torch.manual_seed(37)
+    x = _f(K, R, C) * 1.5 + 0.25
+    g, b = torch.rand(K, C, device=DEV) + 0.5, _f(K, C)
+    vr = torch.tensor([40, 17], dtype=torch.int32, device=DEV)
+    _, mean, rstd, mask = hip.bn_fwd(x, g, b, vr, True, None, with_mask=True)
+    assert mask is not None
+    dy = _f(K, R, C)
+    g1, b1 = torch.empty(K, C, device=DEV), torch.empty(K, C, device=DEV)
+    dx, _ = hip.bn_bwd(dy, x, None, mean, rstd, g, vr, True, g1, b1, False, relu_mask=mask)
+    coef = torch.empty((K, C, 3), device=DEV)
+    g2, b2 = torch.empty(K, C, device=DEV), torch.empty(K, C, device=DEV)
+    assert hip.bn_bwd(dy, x, None, mean, rstd, g, vr, True, g2, b2, False, relu_mask=mask, coef_out=coef) is None
+    assert torch.equal(g1, g2) and torch.equal(b1, b2)
+    out = torch.full((K, R, C), 7.0, device=DEV)
+    hip.bn_bwd_apply_f32(dy, x, mask, coef, vr, out)
+    assert torch.equal(out, dx)
 
 
 @pytest.mark.parametrize("case", [(2, 2, 32, 64, 64), (2, 2, 16, 128, 128), (2, 2, 4, 512, 512)])
