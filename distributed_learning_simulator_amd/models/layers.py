@@ -156,18 +156,15 @@ class BatchNorm(Module):
     def own_params(self):
         return [self.gamma, self.beta]
 
-    def forward(self, x, ctx, residual=None, relu=None, link=None, stats=None, planes: int = 0):
-        """`planes`: the output's consumers are split-plane convs (Fn.batch_norm): 1 = they and
-        fp32 readers, 2 = split-plane convs only. Effective while the weights' planes are live
-        (training steps with BoundParams.split); otherwise the output is plain fp32. 4: the output
-        is read only as the next BatchNorm's residual, which folds this apply into its own. 5: one
-        3x3 stride-1 conv and the next BatchNorm (as its residual) read it, and apply it themselves."""
+    def forward(self, x, ctx, residual=None, relu=None, link=None, stats=None, planes=Fn.BNOut.FP32):
+        """`planes`: the form the output's readers take (Fn.BNOut); split planes only while the weights'
+        planes are live (training steps with BoundParams.split), plain fp32 otherwise."""
         P = ctx.P
         rps = 1
         for d in x.shape[2:-1]:
             rps *= d
-        if (getattr(P, "split", None) is None or self.c % 32) and planes != 4:
-            planes = 0
+        if Fn.BNOut(planes).reads_planes and (getattr(P, "split", None) is None or self.c % 32):
+            planes = Fn.BNOut.FP32
         return Fn.batch_norm(x, ctx.token, P.w(self.gamma), P.w(self.beta), P.g(self.gamma), P.g(self.beta),
                              ctx.valid_rows(rps), self.relu if relu is None else relu, residual, link=link,
                              stats=stats, planes=planes)
@@ -193,12 +190,11 @@ class GroupNorm(Module):
     def own_params(self):
         return [self.gamma, self.beta]
 
-    def forward(self, x, ctx, residual=None, relu=None, link=None, planes: int = 0):
-        """`planes`: BatchNorm.forward's codes, so one block definition serves both norms. Every
-        code whose readers include a split-plane conv (1, 2, 3, 5) gives fp32 + planes here (no
-        planes-only or deferred forms); 0 and 4 (read only as a residual) give fp32."""
+    def forward(self, x, ctx, residual=None, relu=None, link=None, planes=Fn.BNOut.FP32):
+        """`planes`: BatchNorm.forward's forms, so one block definition serves both norms: fp32 + planes
+        where a reader takes planes (no planes-only or deferred forms here), fp32 otherwise."""
         P = ctx.P
-        want = planes not in (0, 4) and getattr(P, "split", None) is not None and self.c % 32 == 0
+        want = Fn.BNOut(planes).reads_planes and getattr(P, "split", None) is not None and self.c % 32 == 0
         return Fn.group_norm(x, ctx.token, P.w(self.gamma), P.w(self.beta), P.g(self.gamma), P.g(self.beta),
                              self.groups, ctx.valid, self.relu if relu is None else relu, residual, link=link,
                              planes=want)

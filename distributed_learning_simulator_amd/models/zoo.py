@@ -99,9 +99,9 @@ def _residual_link(block, x, ctx):
 def _down(seq: Seq, x, ctx, donor=None):
     """Downsample shortcut Seq(Conv2d 1x1, BatchNorm) with epilogue statistics; `donor`: the
     shortcut conv's input gradient goes to the block's first conv (Fn.ResidualLink). Its BN output
-    is read only as the block's last BN's residual, which applies it (batch_norm planes=4)."""
+    is read only as the block's last BN's residual, which applies it (Fn.BNOut.RES_FOLD)."""
     conv, bn = seq.children
-    return conv_bn(conv, bn, x, ctx, conv_donor=donor, planes=4)
+    return conv_bn(conv, bn, x, ctx, conv_donor=donor, planes=Fn.BNOut.RES_FOLD)
 
 
 class BasicBlock(Module):
@@ -118,14 +118,14 @@ class BasicBlock(Module):
         if stride != 1 or cin != cout:
             self.down = self.child("downsample", Seq(Conv2d(cin, cout, 1, stride, 0), norm(cout)))
 
-    def forward(self, x, ctx, out_planes: int = 1):
-        """`out_planes`: what reads the block output (ResNetNet.forward) — 1: the next block's convs
-        (planes) and its identity shortcut (fp32); 2: convs only (a downsample block follows);
-        0: the pooling head only (fp32)."""
+    def forward(self, x, ctx, out_planes: Fn.BNOut = Fn.BNOut.BOTH):
+        """`out_planes`: what reads the block output (ResNetNet.forward) — BOTH: the next block's convs
+        (planes) and its identity shortcut (fp32); PLANES: convs only (a downsample block follows);
+        FP32: the pooling head only."""
         link = _residual_link(self, x, ctx)
         # bn1's output feeds conv2 only: its apply pass is deferred into conv2's halo loader where
         # the shape allows (Fn.DeferredBN), planes only otherwise (fp32 GEMMs, Fn.batch_norm)
-        out = conv_bn(self.conv1, self.bn1, x, ctx, conv_link=link, planes=3)
+        out = conv_bn(self.conv1, self.bn1, x, ctx, conv_link=link, planes=Fn.BNOut.CONV_DEFER)
         sc = x if self.down is None else _down(self.down, x, ctx, donor=link)
         return conv_bn(self.conv2, self.bn2, out, ctx, residual=sc, relu=True,
                        link=link if self.down is None else None, planes=out_planes)
@@ -148,11 +148,11 @@ class Bottleneck(Module):
         if stride != 1 or cin != cout:
             self.down = self.child("downsample", Seq(Conv2d(cin, cout, 1, stride, 0), norm(cout)))
 
-    def forward(self, x, ctx, out_planes: int = 1):
+    def forward(self, x, ctx, out_planes: Fn.BNOut = Fn.BNOut.BOTH):
         """`out_planes`: as BasicBlock.forward."""
         link = _residual_link(self, x, ctx)
-        out = conv_bn(self.conv1, self.bn1, x, ctx, conv_link=link, planes=2)
-        out = conv_bn(self.conv2, self.bn2, out, ctx, planes=2)
+        out = conv_bn(self.conv1, self.bn1, x, ctx, conv_link=link, planes=Fn.BNOut.PLANES)
+        out = conv_bn(self.conv2, self.bn2, out, ctx, planes=Fn.BNOut.PLANES)
         sc = x if self.down is None else _down(self.down, x, ctx, donor=link)
         return conv_bn(self.conv3, self.bn3, out, ctx, residual=sc, relu=True,
                        link=link if self.down is None else None, planes=out_planes)
@@ -190,10 +190,11 @@ class ResNetNet(Module):
         blocks = [b for s in self.stages for b in s.children]
         # the CIFAR stem's BN output is read by the first block's conv1 (planes) and, when that block
         # is an identity-shortcut BasicBlock, by its bn2 as the residual (fp32): both can apply the BN
-        # themselves (Fn.batch_norm planes=5). Otherwise one apply pass writes fp32 + planes
+        # themselves (Fn.BNOut.STEM_DEFER). Otherwise one apply pass writes fp32 + planes
         first = blocks[0] if blocks else None
         two_reader = self.cifar_stem and isinstance(first, BasicBlock) and first.down is None
-        x = conv_bn(self.conv1, self.bn1, x, ctx, planes=0 if not self.cifar_stem else 5 if two_reader else 1)
+        x = conv_bn(self.conv1, self.bn1, x, ctx, planes=Fn.BNOut.FP32 if not self.cifar_stem
+                    else Fn.BNOut.STEM_DEFER if two_reader else Fn.BNOut.BOTH)
         if not self.cifar_stem:
             x = self.maxpool.forward(x, ctx)
         # each block output is written in the form(s) its readers take: split planes only when a
@@ -202,7 +203,7 @@ class ResNetNet(Module):
         # shortcut's residual add)
         for i, b in enumerate(blocks):
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
-            op = 0 if nxt is None else 2 if nxt.down is not None else 1
+            op = Fn.BNOut.FP32 if nxt is None else Fn.BNOut.PLANES if nxt.down is not None else Fn.BNOut.BOTH
             x = b.forward(x, ctx, out_planes=op)
         x = Fn.global_avg_pool(x)
         return self.fc.forward(x, ctx)

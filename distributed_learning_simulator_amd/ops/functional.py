@@ -16,278 +16,29 @@ import torch
 
 from ..options import OPTIONS
 from . import backend, ref
+from .fusion import (BNBwdLink, BNOut, BNStats, DeferredBN, DeferredBNBwd, DeferredRes, DeferredStemBN,  # noqa: F401
+                     MaskedGrad, ResidualLink, Tags, _require_fp32, bn_bwd_defer_count,
+                     bn_bwd_f32_defer_count, bn_bwd_parts_count, res_fold_count, stem_defer_count, tag, tags)
 
 
 def _be(t):
     return backend.get(t)
 
 
+def _given(**kw):
+    """`kw` without its None values: optional operands of calls that ops.ref takes without them."""
+    return {k: v for k, v in kw.items() if v is not None}
+
+
 # --------------------------------------------------------------------------- conv2d
-class ResidualLink:
-    """Hands a second gradient of a residual block's input to the block's first conv, whose
-    dgrad adds it in its epilogue: autograd then never materialises `dX_conv + dX_other` with a
-    separate add pass over the block input.
-    - identity shortcut: the block's last BN (whose backward runs first) deposits dX_shortcut;
-    - downsample shortcut: the shortcut conv (`donor`) deposits its dX. Autograd normally runs
-      it before the main branch reaches the first conv; if not, the first conv marks
-      `receiver_done` and the donor returns its dX to autograd as usual (same result).
-      A 1x1 stride-s donor (fp32 native) deposits only the stride grid — the only pixels its dX
-      is non-zero on — as a dense [K, B, ceil(H/s), ceil(W/s), C] tensor (`compact` = s): one
-      stride-1 GEMM instead of s² parity launches (s² − 1 of them writing zeros), and the
-      receiver's class-(0, 0) launch alone reads it (ops.hip.conv_dgrad acc_compact)."""
+def _halo_shape(w, stride, pad) -> bool:
+    """The shape the LDS-halo kernels serve: 3x3, stride 1, pad 1."""
+    return stride == 1 and pad == 1 and w.shape[2] == 3 and w.shape[3] == 3
 
-    __slots__ = ("grad", "receiver_done", "compact", "receiver_stride")
 
-    def __init__(self):
-        self.grad = None
-        self.receiver_done = False
-        self.compact = 0
-        self.receiver_stride = 1  # stride of the receiving conv (set by its forward)
-
-
-class MaskedGrad:
-    """A gradient g = dy · relu' kept as its factors: `dy` [K, ..., C] fp32 and the 1-bit ReLU mask
-    [K, rows, C / 8]. The identity shortcut of a ResNet block hands its gradient to the block's first
-    conv this way (ResidualLink.grad): that conv's dgrad epilogue gates dy by the bits while it adds
-    it (ops.hip.conv_dgrad acc_mask), so the BN backward never writes dy·relu' and nobody reads it
-    back. `dense()` builds the tensor for any other consumer."""
-
-    __slots__ = ("dy", "mask")
-
-    def __init__(self, dy, mask):
-        self.dy, self.mask = dy, mask
-
-    def dense(self):
-        K, C = self.dy.shape[0], self.dy.shape[-1]
-        bits = torch.arange(8, device=self.mask.device, dtype=torch.uint8)
-        keep = ((self.mask.view(K, -1, C // 8, 1) >> bits) & 1).reshape(K, -1, C).bool()
-        return torch.where(keep, self.dy.reshape(K, -1, C), torch.zeros((), dtype=self.dy.dtype,
-                                                                          device=self.dy.device)).view(self.dy.shape)
-
-
-# A/B switches (BN statistics from the conv epilogue, BN backward partials, split planes, ...)
-# live in options.OPTIONS and are read when an op runs
-
-
-class BNStats:
-    """Links a conv to the BatchNorm that consumes its output:
-    - statistics: the fp32 conv epilogue writes per-32-row Σy / Σy² partials (of the first
-      `valid[k]` samples' rows) and the BN consumes them instead of re-reading y in a statistics
-      pass. `part` stays None when the producing conv could not provide them (CPU oracle, bf16
-      kernels, LDS-DMA path);
-    - `dy_planes_ok`: the conv runs its dgrad and wgrad on split planes (csrc/conv_pl.hip), so
-      the BN backward writes only dX's planes (ops.hip.bn_bwd dx_planes=2), never the fp32 dX."""
-
-    __slots__ = ("valid", "part", "dy_planes_ok", "wgrad_bn_bwd_ok")
-
-    def __init__(self, valid=None):
-        self.valid = valid
-        self.part = None
-        self.dy_planes_ok = False
-        # the conv's weight gradient is its backward's only reader of dY and can apply the BN
-        # backward in its fp32 dY loader (DeferredBNBwdF32)
-        self.wgrad_bn_bwd_ok = False
-
-
-# BN backward passes that used a dgrad's partials ("used"), whose consumer wrote none (a strided
-# or absent conv: "none"), or whose dY was not that dgrad's output ("fallback"): tests, reports
-bn_bwd_parts_count = {"used": 0, "none": 0, "fallback": 0}
-
-
-class BNBwdLink:
-    """Links a training BatchNorm's output to the stride-1 conv that consumes it: that conv's dgrad
-    epilogue writes the BN backward's partial sums Σĝ, Σĝ·x̂ (ĝ = dY·relu') while it stores dX
-    (= the BN's dY), so the BN backward skips its reduction pass over dY and x (ops.hip.conv_dgrad
-    bnb=). The BN uses them only if the dY autograd hands it is that very dgrad output, unmodified
-    (`key` = storage pointer + version): any other gradient summed in (a second consumer, a late
-    residual donor) makes it fall back to its own pass."""
-
-    __slots__ = ("x", "mask", "mean", "rstd", "valid", "part", "key")
-
-    def __init__(self, x, mask, mean, rstd, valid):
-        self.x, self.mask, self.mean, self.rstd, self.valid = x, mask, mean, rstd, valid
-        self.part = None
-        self.key = None
-
-    def args(self, part):
-        return (part, self.x, self.mask, self.mean, self.rstd, self.valid, None)
-
-
-# Split-plane operands (csrc/conv_pl.hip). A tensor produced together with its bf16 (hi, lo)
-# planes carries them as attribute `_dls_planes` ([K, 2, *shape[1:]], ops.hip.planes_buffer
-# layout); `_dls_planes_only` marks a tensor whose fp32 bytes ARE those planes (the producer
-# wrote nothing else) — only a planes-reading GEMM may consume it. OPTIONS.planes = False
-# disables them.
-
-
-def _planes_of(t):
-    return getattr(t, "_dls_planes", None)
-
-
-def _tag_planes(t, planes, only: bool):
-    t._dls_planes = planes
-    t._dls_planes_only = only
-    return t
-
-
-def _require_fp32(t, who: str):
-    if getattr(t, "_dls_planes_only", False):
-        raise RuntimeError(f"{who}: a planes-only activation reached an op that reads fp32 values")
-
-
-class DeferredBN:
-    """A BatchNorm(+ReLU) output whose apply pass is deferred to its one consumer, a 3x3 stride-1
-    conv that applies it while staging its input (ops.hip.conv_halo_bn_fwd, csrc/conv_halo.hip
-    BNF): the normalised activation is never read back from HBM. The BN hands autograd the
-    planes-only alias of `yp` (batch_norm planes=3); in training the fused conv also writes the
-    planes and ReLU bits (its weight gradient and the BN backward read them). A consumer that
-    cannot fuse — or anything that needs the values first — calls `materialize()`, which runs
-    the ordinary apply pass into the same buffers. Bits are identical either way."""
-
-    __slots__ = ("x", "coef", "relu", "valid_rows", "yp", "mask", "write_out", "pending")
-
-    def __init__(self, x, coef, relu, valid_rows, yp, mask, write_out):
-        self.x, self.coef, self.relu, self.valid_rows = x, coef, relu, valid_rows
-        self.yp, self.mask, self.write_out = yp, mask, write_out
-        self.pending = True
-
-    def materialize(self):
-        if self.pending:
-            from . import hip
-
-            hip.bn_apply_only(self.x, self.coef, self.valid_rows, self.relu, self.yp, self.mask)
-            self.pending = False
-
-
-# two-reader deferred BNs (DeferredStemBN): applies taken by the halo conv ("conv") or folded into
-# the next BN's residual add ("res"), and forms written by a pass of their own ("materialized")
-stem_defer_count = {"conv": 0, "res": 0, "materialized": 0}
-
-
-class DeferredStemBN(DeferredBN):
-    """A DeferredBN with a second reader: the next BatchNorm, which takes the output as its residual
-    (batch_norm planes=5: the CIFAR ResNet stem BN, read by layer1.0.conv1 and, through the identity
-    shortcut, by layer1.0.bn2). The conv side is DeferredBN's (`pending`, `materialize()`: planes +
-    ReLU bits). The residual side folds the apply into the reading BN (hip.bn_fwd res_coef +
-    res_relu: the fp32 bits this BN's own pass would have stored) or calls `materialize_f32()`, which
-    writes the fp32 form into a tensor of its own. The two readers are independent and each form is
-    written at most once. The tensor autograd carries is the planes-only alias: a reader that knows
-    neither side fails (_require_fp32)."""
-
-    __slots__ = ("y32",)
-
-    def __init__(self, x, coef, relu, valid_rows, yp, mask, write_out):
-        super().__init__(x, coef, relu, valid_rows, yp, mask, write_out)
-        self.y32 = None
-
-    def materialize(self):
-        if self.pending:
-            stem_defer_count["materialized"] += 1
-        super().materialize()
-
-    def materialize_f32(self):
-        if self.y32 is None:
-            from . import hip
-
-            self.y32 = torch.empty(self.x.shape, dtype=self.x.dtype, device=self.x.device)
-            hip.bn_apply_only(self.x, self.coef, self.valid_rows, self.relu, None, y=self.y32)
-            stem_defer_count["materialized"] += 1
-        return self.y32
-
-
-# downsample BN applies folded into the next BN ("folded") or run as their own pass ("materialized")
-res_fold_count = {"folded": 0, "materialized": 0}
-
-
-class DeferredRes:
-    """A BatchNorm output without ReLU whose one reader is the next BatchNorm, as its residual — a
-    ResNet downsample shortcut's BN (batch_norm planes=4): the statistics and (scale, shift) are
-    computed, the output is never written, and the reader folds the apply into its own
-    (hip.bn_fwd res_coef: act(bn2(x) + scale·x_ds + shift), the bits of applying it first). The
-    backward needs no output (no ReLU). Anything else that needs the values calls materialize(),
-    the ordinary apply pass into the same tensor."""
-
-    __slots__ = ("x", "coef", "valid_rows", "y", "pending")
-
-    def __init__(self, x, coef, valid_rows, y):
-        self.x, self.coef, self.valid_rows, self.y = x, coef, valid_rows, y
-        self.pending = True
-
-    def materialize(self):
-        if self.pending:
-            from . import hip
-
-            hip.bn_apply_only(self.x, self.coef, self.valid_rows, False, None, y=self.y)
-            self.pending = False
-            res_fold_count["materialized"] += 1
-
-
-# deferred BN backward applies (DeferredBNBwd) taken by a halo weight gradient's loader ("wgrad")
-# or run as their own pass ("materialized"): tests, reports
-bn_bwd_defer_count = {"wgrad": 0, "materialized": 0}
-
-
-class DeferredBNBwd:
-    """A training BatchNorm's input gradient dX whose apply pass is deferred to the conv that
-    produced the BN's input (OPTIONS.bn_bwd_in_wgrad): the BN backward computed only its
-    coefficients (a, d, e) and dγ / dβ, and hands autograd the planes-only alias of an unwritten
-    `dxp`. That conv's backward runs its halo weight gradient first, in dY mode 2
-    (csrc/conv_halo_wgrad.hip), which builds dX = a·(dy·relu') + e·x + d in its loader and stores
-    the planes for the dgrad on the way; any other consumer calls `materialize()` — the ordinary
-    apply pass into the same planes, with the same bits."""
-
-    __slots__ = ("dy", "x", "mask", "coef", "valid_rows", "dxp", "pending")
-
-    def __init__(self, dy, x, mask, coef, valid_rows, dxp):
-        self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dxp = dy, x, mask, coef, valid_rows, dxp
-        self.pending = True
-
-    def materialize(self):
-        if self.pending:
-            from . import hip
-
-            hip.bn_bwd_apply_planes(self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dxp)
-            self.pending = False
-            bn_bwd_defer_count["materialized"] += 1
-
-    def wgrad_args(self):
-        return (self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dxp)
-
-
-# deferred BN backward applies (DeferredBNBwdF32) taken by an fp32 weight gradient's loader
-# ("wgrad") or run as their own pass ("materialized"): tests, reports
-bn_bwd_f32_defer_count = {"wgrad": 0, "materialized": 0}
-
-
-class DeferredBNBwdF32:
-    """A training BatchNorm's input gradient dX whose apply pass is deferred to the conv that
-    produced the BN's input, when that conv's backward is a weight gradient alone (its input needs no
-    gradient: the ResNet stem; OPTIONS.bn_bwd_in_wgrad_f32). The BN backward computed only its
-    coefficients (a, d, e) and dγ / dβ and hands autograd the unwritten fp32 tensor `dx`, tagged
-    unreadable (_require_fp32). The conv's fp32 TN weight gradient builds dX = a·(dy·relu') + e·x + d
-    in its dY loader (ops.hip.conv_wgrad bn_bwd=); any other consumer calls `materialize()` — the
-    ordinary apply pass into `dx`, with the same bits — which clears the tag."""
-
-    __slots__ = ("dy", "x", "mask", "coef", "valid_rows", "dx", "pending")
-
-    def __init__(self, dy, x, mask, coef, valid_rows, dx):
-        self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dx = dy, x, mask, coef, valid_rows, dx
-        self.pending = True
-
-    def materialize(self, holder=None):
-        """`holder`: the tensor autograd delivered (an alias of `dx`), whose tag is cleared too."""
-        if self.pending:
-            from . import hip
-
-            hip.bn_bwd_apply_f32(self.dy, self.x, self.mask, self.coef, self.valid_rows, self.dx)
-            self.pending = False
-            bn_bwd_f32_defer_count["materialized"] += 1
-        for t in (self.dx, holder):
-            if t is not None:
-                t._dls_planes_only = False
-
-    def wgrad_args(self):
-        return (self.dy, self.x, self.mask, self.coef, self.valid_rows)
+def _stats_part(be, K, rows, C, device):
+    """An epilogue's per-32-row partial sums [K, parts, 2, C] (BN statistics, BN backward sums)."""
+    return torch.empty((K, be.conv_stats_parts(rows), 2, C), dtype=torch.float32, device=device)
 
 
 class _Conv(torch.autograd.Function):
@@ -309,10 +60,11 @@ class _Conv(torch.autograd.Function):
         if be is ref or x.dtype != torch.float32:
             w_split = None
         # split-plane GEMMs: x's planes (from the producing BN) + the weight planes
-        xp = _planes_of(x)
+        tx = tags(x)
+        xp = tx.planes
         use_pl = (xp is not None and w_split is not None and x.is_contiguous()
                   and be.conv_planes_ok(x.shape[-1], w.shape[1]) and be.planes_fit(x[0].numel()))
-        if getattr(x, "_dls_planes_only", False) and not use_pl:
+        if tx.planes_only and not use_pl:
             raise RuntimeError("conv2d: planes-only input but the split-plane GEMM cannot run here")
         pl = {"x_planes": xp} if use_pl else {}
         ctx.xp = xp if use_pl else None
@@ -329,15 +81,14 @@ class _Conv(torch.autograd.Function):
         want_stats = stats is not None and be is not ref and x.dtype == torch.float32 and not big
         y = None
         ctx.bn_src = None
-        defer = getattr(x, "_dls_bn_defer", None)
+        defer = tx.bn_defer
         if defer is not None and defer.pending:
             # a deferred BN input (DeferredBN): apply it in this conv's halo loader if it can
             # (bn_fused_halo off: a two-reader deferral's conv side materialises; a DeferredBN is
             # never created then)
-            if (OPTIONS.bn_fused_halo and use_pl and stride == 1 and pad == 1 and KH == 3 and w.shape[3] == 3
-                    and b is None and be.halo_bn_ok(x.shape, w)):
-                part = (torch.empty((K, be.conv_stats_parts(B * OH * OW), 2, w.shape[1]), dtype=torch.float32,
-                                    device=x.device) if want_stats else None)
+            if (OPTIONS.bn_fused_halo and use_pl and _halo_shape(w, stride, pad) and b is None
+                    and be.halo_bn_ok(x.shape, w)):
+                part = _stats_part(be, K, B * OH * OW, w.shape[1], x.device) if want_stats else None
                 # the weight gradient applies the BN in its own loader too (halo wgrad x mode 2): then
                 # the normalised planes are never written, only the ReLU bits the BN backward reads
                 bn_wgrad = (defer.write_out and gw is not None and OPTIONS.halo_wgrad
@@ -347,27 +98,19 @@ class _Conv(torch.autograd.Function):
                                         yp=defer.yp if defer.write_out and not bn_wgrad else None,
                                         mask=defer.mask if defer.write_out else None)
                 if y is not None:
-                    defer.pending = False
-                    if isinstance(defer, DeferredStemBN):
-                        stem_defer_count["conv"] += 1
+                    defer.taken("conv")
                     if want_stats:
                         stats.part = part
                     if bn_wgrad:
                         ctx.bn_src = (defer.x.view(x.shape), defer.coef, defer.relu, defer.valid_rows)
             defer.materialize()
-        if y is not None:
-            pass
-        elif want_stats:
-            stats.part = torch.empty((K, be.conv_stats_parts(B * OH * OW), 2, w.shape[1]), dtype=torch.float32,
-                                     device=x.device)
-            y = be.conv_fwd(x, w, stride, pad, bias=b, stats=stats.part, stats_valid=stats.valid,
-                            **({"w_split": w_split} if w_split is not None else {}), **pl)
-        elif w_split is not None:
-            y = be.conv_fwd(x, w, stride, pad, bias=b, w_split=w_split, **pl)
-        else:
-            y = be.conv_fwd(x, w, stride, pad, bias=b)
+        if y is None:
+            if want_stats:
+                stats.part = _stats_part(be, K, B * OH * OW, w.shape[1], x.device)
+            st = {"stats": stats.part, "stats_valid": stats.valid} if want_stats else {}
+            y = be.conv_fwd(x, w, stride, pad, bias=b, **st, **pl, **_given(w_split=w_split))
         # the backward is a weight gradient alone, on the fp32 TN kernel: the consuming BN may leave its
-        # backward's apply pass to that kernel's dY loader (DeferredBNBwdF32)
+        # backward's apply pass to that kernel's dY loader (DeferredBNBwd f32)
         ctx.wgrad_bn_bwd = bool(
             OPTIONS.bn_bwd_in_wgrad_f32 and stats is not None and be is not ref and x.dtype == torch.float32
             and not ctx.needs_input_grad[0] and link is None and donor is None and b is None and gw is not None
@@ -377,10 +120,10 @@ class _Conv(torch.autograd.Function):
             stats.wgrad_bn_bwd_ok = ctx.wgrad_bn_bwd
         ctx.w_split = w_split
         # the consuming BN will hand the backward dY as planes only: a dY without them (a tensor
-        # rebuilt on the way, which drops the _dls_planes attributes) must fail, not be read as fp32
+        # rebuilt on the way, which drops its tags) must fail, not be read as fp32
         ctx.expect_dy_planes = stats is not None and stats.dy_planes_ok
-        ctx.x_planes_only = bool(getattr(x, "_dls_planes_only", False))
-        bnb = getattr(x, "_dls_bnb", None) if OPTIONS.bn_bwd_parts else None
+        ctx.x_planes_only = tx.planes_only
+        bnb = tx.bnb if OPTIONS.bn_bwd_parts else None
         # (the dgrad writes the partials only in one launch: a dY or dX window past 2 GiB runs
         # batch-chunked, e.g. a 64 -> 256 1x1 conv whose output alone crosses it)
         if bnb is not None and not (be is not ref and donor is None and x.shape[-1] == ci and not big
@@ -404,11 +147,11 @@ class _Conv(torch.autograd.Function):
     def _wgrad(ctx, dy, x, w, dyp, be, bbd=None, sgd_ok=True, bbf=None) -> bool:
         """The weight gradient (or the SGD step fused into it). `bbd` (DeferredBNBwd): only the halo
         kernel's BN-backward dY mode — returns False, launching nothing, when it cannot serve;
-        `sgd_ok` False: store dW (the flat step covers the weight). `bbf` (DeferredBNBwdF32, a
-        backward whose forward set ctx.wgrad_bn_bwd): the fp32 TN kernel's BN-backward dY loader, a
-        plain store of dW."""
+        `sgd_ok` False: store dW (the flat step covers the weight). `bbf` (its f32 kind, a backward
+        whose forward set ctx.wgrad_bn_bwd): the fp32 TN kernel's BN-backward dY loader, a plain
+        store of dW."""
         if bbd is not None:
-            if not (ctx.stride == 1 and ctx.pad == 1 and w.shape[2] == 3 and w.shape[3] == 3):
+            if not _halo_shape(w, ctx.stride, ctx.pad):
                 return False
             sgd = ctx.sgd if sgd_ok else None
             if ctx.bn_src is not None:
@@ -438,9 +181,8 @@ class _Conv(torch.autograd.Function):
                                  sgd=sgd):
                 raise RuntimeError("conv2d backward: the halo wgrad refused a shape its forward accepted")
             stepped = sgd is not None
-        elif (ctx.halo_wgrad and ctx.stride == 1 and ctx.pad == 1 and w.shape[2] == 3 and w.shape[3] == 3
-              and not padded and be.halo_wgrad(dy, x, gw, dy_planes=dyp, x_planes=ctx.xp, valid=ctx.valid,
-                                               sgd=sgd)):
+        elif (ctx.halo_wgrad and _halo_shape(w, ctx.stride, ctx.pad) and not padded
+              and be.halo_wgrad(dy, x, gw, dy_planes=dyp, x_planes=ctx.xp, valid=ctx.valid, sgd=sgd)):
             stepped = sgd is not None
         elif dyp is not None:
             stepped = be.conv_wgrad(dy, x, gw, ctx.stride, ctx.pad, dy_planes=dyp, x_planes=ctx.xp, sgd=sgd)
@@ -483,12 +225,12 @@ class _Conv(torch.autograd.Function):
             link.compact = 0
             if acc is None:
                 link.receiver_done = True  # (a late donor hands its dX to autograd instead)
-        dyp = _planes_of(dy)
+        dyp = tags(dy).planes
         wgrad_done = False
         wt_pre = None
-        bbd = getattr(dy, "_dls_bnbwd", None)
-        if bbd is not None and bbd.pending:
-            # dY is a deferred BN input gradient (DeferredBNBwd): the halo weight gradient applies
+        bb = tags(dy).bn_bwd
+        if bb is not None and bb.pending and not bb.f32:
+            # dY is a deferred BN input gradient (DeferredBNBwd, planes): the halo weight gradient applies
             # the BN backward in its loader and writes dY's planes, so it runs before the dgrad
             if ctx.gw is not None and be is not ref and ctx.halo_wgrad and w.shape[-1] == ctx.ci:
                 sgd_ok = True
@@ -499,23 +241,21 @@ class _Conv(torch.autograd.Function):
                               if ctx.dgrad_wt and ctx.w_split is not None and not acc_compact and ctx.donor is None
                               else None)
                     sgd_ok = wt_pre is not None
-                wgrad_done = _Conv._wgrad(ctx, dy, x, w, dyp, be, bbd, sgd_ok=sgd_ok)
+                wgrad_done = _Conv._wgrad(ctx, dy, x, w, dyp, be, bb, sgd_ok=sgd_ok)
             if wgrad_done:
-                bbd.pending = False
-                bn_bwd_defer_count["wgrad"] += 1
+                bb.taken("wgrad")
             else:
-                bbd.materialize()
-        bbf = getattr(dy, "_dls_bnbwd_f32", None)
-        if bbf is not None and bbf.pending:
-            # dY is a deferred BN input gradient, unwritten (DeferredBNBwdF32): the fp32 weight
+                bb.materialize()
+        elif bb is not None and bb.pending:
+            # dY is a deferred BN input gradient, unwritten (DeferredBNBwd, f32): the fp32 weight
             # gradient, this backward's only reader of it, applies the BN backward in its loader
             if ctx.wgrad_bn_bwd and not ctx.needs_input_grad[0] and acc is None and dyp is None:
-                _Conv._wgrad(ctx, dy, x, w, None, be, bbf=bbf)
+                _Conv._wgrad(ctx, dy, x, w, None, be, bbf=bb)
                 wgrad_done = True
-                bbf.pending = False
-                bn_bwd_f32_defer_count["wgrad"] += 1
+                bb.taken("wgrad")
             else:
-                bbf.materialize(dy)
+                bb.materialize()
+                tags(dy).planes_only = False  # (written now: this backward may read it)
         if dyp is not None and ctx.xp is None:
             raise RuntimeError("conv2d backward: dY planes without the input's planes")
         if dyp is None:
@@ -530,31 +270,19 @@ class _Conv(torch.autograd.Function):
         if ctx.needs_input_grad[0] and compact:
             # 1x1 stride-s downsample shortcut: dX is non-zero only on the stride grid, where it is
             # the stride-1 1x1 dgrad of dY — computed compactly and handed to the block's first conv
-            dx = be.conv_dgrad(dy, w, dy.shape[2:4], 1, 0, w_split=ctx.w_split,
-                               **({"dy_planes": dyp} if dyp is not None else {}))
+            dx = be.conv_dgrad(dy, w, dy.shape[2:4], 1, 0, w_split=ctx.w_split, **_given(dy_planes=dyp))
         elif ctx.needs_input_grad[0]:
             if acc_compact:
                 dx = be.conv_dgrad(dy, w, x.shape[2:4], ctx.stride, ctx.pad, acc=acc, w_split=ctx.w_split,
-                                   acc_compact=True, **({"dy_planes": dyp} if dyp is not None else {}))
+                                   acc_compact=True, **_given(dy_planes=dyp))
             else:
-                kw = {}
                 bnb = ctx.bnb
                 if bnb is not None:
                     K, B, H, W, Ci = x.shape
-                    part = torch.empty((K, be.conv_stats_parts(B * H * W), 2, Ci), dtype=torch.float32,
-                                       device=dy.device)
-                    kw["bnb"] = bnb.args(part)
-                if dyp is not None:
-                    kw["dy_planes"] = dyp
-                if ctx.w_split is not None:
-                    kw["w_split"] = ctx.w_split
-                if acc_mask is not None:
-                    kw["acc_mask"] = acc_mask
-                if ctx.dgrad_wt:
-                    kw["wt"] = True
-                if wt_pre is not None:
-                    kw["wt_buf"] = wt_pre
-                dx = be.conv_dgrad(dy, w, x.shape[2:4], ctx.stride, ctx.pad, acc=acc, **kw)
+                    part = _stats_part(be, K, B * H * W, Ci, dy.device)
+                dx = be.conv_dgrad(dy, w, x.shape[2:4], ctx.stride, ctx.pad, acc=acc, **_given(
+                    bnb=bnb.args(part) if bnb is not None else None, dy_planes=dyp, w_split=ctx.w_split,
+                    acc_mask=acc_mask, wt=True if ctx.dgrad_wt else None, wt_buf=wt_pre))
                 if bnb is not None:
                     bnb.part, bnb.key = part, (dx.data_ptr(), dx._version)
             if dx.shape[-1] > ctx.ci:
@@ -598,7 +326,7 @@ class _Linear(torch.autograd.Function):
     Split planes (fp32 native, with the weight's planes `w_split`; csrc/conv_pl.hip):
     x_planes  — x's planes (a LayerNorm / planes-writing linear output): the forward GEMM and
                 the weight gradient read them;
-    out_planes— the epilogue also writes y's planes (tagged `_dls_planes`) for the next linear;
+    out_planes— the epilogue also writes y's planes (tags(y).planes) for the next linear;
     dx_planes — the dgrad epilogue also writes dX's planes (for the producer's backward);
     a dy arriving with planes, or masked here by the dropout backward (which then writes them),
     feeds the dgrad and the weight gradient as planes. x and y keep their leading shape."""
@@ -639,7 +367,7 @@ class _Linear(torch.autograd.Function):
         ctx.sgd = sgd if (native and gw is not None) else None  # (the plane weight gradient may step W)
         yo = y.view(*shp[:-1], y.shape[-1])
         if yp is not None:
-            _tag_planes(yo, yp.view((shp[0], 2) + tuple(yo.shape[1:])), False)
+            tag(yo, planes=yp.view((shp[0], 2) + tuple(yo.shape[1:])))
         return yo
 
     @staticmethod
@@ -647,7 +375,7 @@ class _Linear(torch.autograd.Function):
         x, w, y, seeds = ctx.saved_tensors
         be = _be(dy)
         K, N, Fi = x.shape
-        dyp = _planes_of(dy) if ctx.native else None
+        dyp = tags(dy).planes if ctx.native else None
         dy = dy.reshape(K, N, -1)
         if dyp is None:
             dy = dy.contiguous()
@@ -704,7 +432,7 @@ class _Linear(torch.autograd.Function):
                 dx = dx + acc.reshape(dx.shape)
             dx = dx.view(ctx.shape)
             if dxp is not None:
-                _tag_planes(dx, dxp.view((K, 2) + tuple(ctx.shape[1:])), False)
+                tag(dx, planes=dxp.view((K, 2) + tuple(ctx.shape[1:])))
         if ctx.gw is not None:
             if be is ref:
                 dw, db = ref.linear_wgrad(dy.float(), x.float(), ctx.gb is not None)
@@ -730,7 +458,7 @@ def linear(x, token, w, b, gw, gb, residual=None, relu=False, premasked=False, g
     """x [K, ..., Fi] -> [K, ..., Fo]. Epilogue fusions and split planes: see _Linear
     (relu / premasked / gate_input / residual / dropout / out_planes / dx_planes). `w_split`: the
     weight's pre-split bf16 planes (BoundParams.ws) for the fp32 GEMMs; x's planes, when it
-    carries them (`_dls_planes`), are read by the plane GEMMs. `res_link` (with `residual`): the
+    carries them (tags(x).planes), are read by the plane GEMMs. `res_link` (with `residual`): the
     residual's gradient is deposited in the link instead of returned; `acc_link`: this linear's
     dgrad adds the link's gradient to dX in its epilogue — give both to the two readers of one
     tensor (the residual add and the next linear) and autograd never adds their gradients in a
@@ -738,7 +466,7 @@ def linear(x, token, w, b, gw, gb, residual=None, relu=False, premasked=False, g
     otherwise the receiver marks the link done and the gradient goes back to autograd."""
     assert not (relu and residual is not None), "ReLU and residual epilogues are not combined"
     return _Linear.apply(x, token, w, b, gw, gb, residual, relu, premasked, gate_input, drop_p, drop_seeds,
-                         gate_scale, w_split, _planes_of(x), out_planes, dx_planes, res_link, acc_link, sgd)
+                         gate_scale, w_split, tags(x).planes, out_planes, dx_planes, res_link, acc_link, sgd)
 
 
 class _LinearSharedInput(torch.autograd.Function):
@@ -780,81 +508,72 @@ def linear_shared_input(x, token, w, gw):
 class _BN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, token, gamma, beta, ggamma, gbeta, valid_rows, relu, residual, link=None, stats=None,
-                planes=0):
+                planes=BNOut.FP32):
         be = _be(x)
         K = x.shape[0]
         C = x.shape[-1]
         _require_fp32(x, "batch_norm")
         x3 = x.reshape(K, -1, C)
-        res_coef = None
+        r3 = res_coef = None
         res_relu = False
-        r3 = None
-        sdef = getattr(residual, "_dls_bn_defer", None) if residual is not None else None
+        sdef = tags(residual).bn_defer
         if isinstance(sdef, DeferredStemBN):
             # the residual is a two-reader deferred BN output: its apply is folded into this one, or
             # its fp32 form is written first (the tensor itself holds planes, or nothing)
             if (be is not ref and x.dtype == torch.float32 and sdef.y32 is None and sdef.valid_rows is valid_rows
                     and sdef.x.shape == x3.shape and x3.is_contiguous() and sdef.x.is_contiguous()):
                 r3, res_coef, res_relu = sdef.x, sdef.coef, sdef.relu
-                stem_defer_count["res"] += 1
+                stem_defer_count["res"] += 1  # (the conv side stays pending: the two readers are independent)
             else:
                 r3 = sdef.materialize_f32().reshape(K, -1, C)
         elif residual is not None:
             _require_fp32(residual, "batch_norm residual")
             r3 = residual.reshape(K, -1, C)
-        mask = None
-        yp = None
-        bnb = None
-        fold = getattr(residual, "_dls_res_fold", None) if residual is not None else None
+        mask = yp = bnb = defer = fold_out = None
+        fold = tags(residual).res_fold
         if fold is not None and fold.pending:
             # a downsample BN's apply folded into this one (DeferredRes), or materialised first
             if (be is not ref and x.dtype == torch.float32 and fold.valid_rows is valid_rows
                     and fold.x.shape == x3.shape and x3.is_contiguous()):
                 r3, res_coef = fold.x, fold.coef
-                fold.pending = False
-                res_fold_count["folded"] += 1
+                fold.taken("folded")
             else:
                 fold.materialize()
-        fold_out = None
         if be is ref:
             y, mean, rstd = be.bn_fwd(x3, gamma, beta, valid_rows, relu, r3)
         else:  # native: 1-bit ReLU mask so the backward need not re-read y
             pre = stats.part if stats is not None else None
-            planes = planes if (OPTIONS.planes and x.dtype == torch.float32 and x.is_contiguous()
-                                and be.planes_fit(x[0].numel())) else 0
+            planes = BNOut(planes) if (OPTIONS.planes and x.dtype == torch.float32 and x.is_contiguous()
+                                       and be.planes_fit(x[0].numel())) else BNOut.FP32
             # (inference passes — evaluation, GTG utilities — write no ReLU mask: no backward reads
             # it. Autograd is off inside Function.forward, so ask which inputs need a gradient)
             wm = any(ctx.needs_input_grad)
             C8 = C % 8 == 0
-            if planes == 3 and not (OPTIONS.bn_fused_halo and residual is None and C8 and x3.is_contiguous()):
-                planes = 2  # (no deferral: apply now, planes only)
-            if planes == 4 and not (OPTIONS.bn_res_fold and residual is None and not relu and x3.is_contiguous()):
-                planes = 0  # (no fold: apply now, fp32)
-            if planes == 5 and not (OPTIONS.bn_stem_defer and residual is None and C8 and x3.is_contiguous()):
-                planes = 1  # (no deferral: apply now, fp32 + planes)
-            if planes == 4:
+            can = {BNOut.CONV_DEFER: OPTIONS.bn_fused_halo and C8, BNOut.RES_FOLD: OPTIONS.bn_res_fold and not relu,
+                   BNOut.STEM_DEFER: OPTIONS.bn_stem_defer and C8}
+            if planes in can and not (can[planes] and residual is None and x3.is_contiguous()):
+                planes = planes.applied_now  # (no deferral / fold: one apply pass, now)
+            if planes is BNOut.RES_FOLD:
                 # the reader (the next BN, as its residual) applies it (DeferredRes)
                 coef, mean, rstd = be.bn_coef(x3, gamma, beta, valid_rows, pre_stats=pre)
                 y = torch.empty((K, x3.shape[1], C), dtype=x.dtype, device=x.device)
                 fold_out = DeferredRes(x3, coef, valid_rows, y)
-                defer = None
-                planes = 0
-            elif planes == 3 or planes == 5:
+            elif planes in (BNOut.CONV_DEFER, BNOut.STEM_DEFER):
                 # deferred apply (DeferredBN): statistics + coefficients now; the consuming 3x3 conv
                 # applies them in its halo loader, or materialises the planes / ReLU bits first
-                # (5, DeferredStemBN: and the next BN, which reads the output as its residual)
+                # (DeferredStemBN: and the next BN, which reads the output as its residual)
                 coef, mean, rstd = be.bn_coef(x3, gamma, beta, valid_rows, pre_stats=pre)
                 y, yp = be.planes_buffer((K, x3.shape[1], C), x.device)
                 mask = torch.empty((K, x3.shape[1], C // 8), dtype=torch.uint8, device=x.device) if (wm and relu) else None
-                defer = (DeferredBN if planes == 3 else DeferredStemBN)(x3, coef, relu, valid_rows, yp, mask,
-                                                                        write_out=wm)
+                defer = (DeferredBN if planes is BNOut.CONV_DEFER else DeferredStemBN)(x3, coef, relu, valid_rows, yp,
+                                                                                       mask, write_out=wm)
             else:
-                defer = None
-                out = be.bn_fwd(x3, gamma, beta, valid_rows, relu, r3, with_mask=wm, pre_stats=pre, planes=planes,
+                # (FP32 / BOTH / PLANES are the kernel's own 0 / 1 / 2)
+                out = be.bn_fwd(x3, gamma, beta, valid_rows, relu, r3, with_mask=wm, pre_stats=pre, planes=int(planes),
                                 res_coef=res_coef, res_relu=res_relu)
                 y, mean, rstd = out[:3]
                 mask = out[3] if wm else None
-                if planes:
+                if planes is not BNOut.FP32:
                     yp = out[-1]
             if stats is not None:
                 stats.part = None
@@ -874,15 +593,11 @@ class _BN(torch.autograd.Function):
         ctx.bwd_in_wgrad = OPTIONS.bn_bwd_in_wgrad
         ctx.bwd_in_wgrad_f32 = OPTIONS.bn_bwd_in_wgrad_f32
         yo = y.reshape(x.shape)
-        if yp is not None:
-            _tag_planes(yo, yp.view((K, 2) + tuple(x.shape[1:])), planes >= 2)
-        ctx.defer = None
-        if be is not ref and planes in (3, 5):
-            yo._dls_bn_defer = ctx.defer = defer
-        if fold_out is not None:
-            yo._dls_res_fold = fold_out
-        if bnb is not None:
-            yo._dls_bnb = bnb
+        if yp is not None:  # (of the forms with planes, BOTH alone also wrote fp32 values)
+            tag(yo, planes=yp.view((K, 2) + tuple(x.shape[1:])), planes_only=planes is not BNOut.BOTH)
+        ctx.defer = defer
+        if defer is not None or fold_out is not None or bnb is not None:
+            tag(yo, bn_defer=defer, res_fold=fold_out, bnb=bnb)
         return yo
 
     @staticmethod
@@ -926,24 +641,22 @@ class _BN(torch.autograd.Function):
                 if masked:
                     ctx.link.grad = MaskedGrad(dy3.view(ctx.shape), ctx.relu_mask)
                 dxo = dx.reshape(ctx.shape)
-                _tag_planes(dxo, dxp.view((K, 2) + tuple(ctx.shape[1:])), True)
-                dxo._dls_bnbwd = DeferredBNBwd(dy3, x3, ctx.relu_mask if ctx.relu else None, coef, ctx.valid_rows,
-                                               dxp)
+                tag(dxo, planes=dxp.view((K, 2) + tuple(ctx.shape[1:])), planes_only=True, bn_bwd=DeferredBNBwd(
+                    dy3, x3, ctx.relu_mask if ctx.relu else None, coef, ctx.valid_rows, dxp))
                 return dxo, None, None, None, None, None, None, None, None, None, None, None
             if (dxm == 0 and ctx.bwd_in_wgrad_f32 and ctx.stats is not None and ctx.stats.wgrad_bn_bwd_ok
                     and not ctx.has_res and C % 8 == 0 and (ctx.relu_mask is not None or not ctx.relu)
                     and x3.is_contiguous() and dy3.dtype == torch.float32):
                 # coefficients only: the producing conv's backward is an fp32 weight gradient alone,
-                # which applies them in its dY loader (DeferredBNBwdF32), or materialize() does
+                # which applies them in its dY loader (DeferredBNBwd f32), or materialize() does
                 coef = torch.empty((K, C, 3), dtype=torch.float32, device=dy3.device)
                 be.bn_bwd(dy3, x3, y, mean, rstd, gamma, ctx.valid_rows, ctx.relu, ctx.ggamma, ctx.gbeta, False,
                           relu_mask=ctx.relu_mask, pre_part=pre, coef_out=coef)
                 dx = torch.empty((K, R, C), dtype=torch.float32, device=dy3.device)
                 dxo = dx.reshape(ctx.shape)
-                _tag_planes(dxo, None, True)  # (unwritten: no fp32 reader may take it as it is)
-                _tag_planes(dx, None, True)
-                dxo._dls_bnbwd_f32 = DeferredBNBwdF32(dy3, x3, ctx.relu_mask if ctx.relu else None, coef,
-                                                      ctx.valid_rows, dx)
+                # (unwritten: no fp32 reader may take it as it is. The deferral holds dx, not the tagged dxo: no cycle)
+                tag(dxo, planes_only=True, bn_bwd=DeferredBNBwd(
+                    dy3, x3, ctx.relu_mask if ctx.relu else None, coef, ctx.valid_rows, dx, f32=True))
                 return dxo, None, None, None, None, None, None, None, None, None, None, None
             out = be.bn_bwd(dy3, x3, y, mean, rstd, gamma, ctx.valid_rows, ctx.relu,
                             ctx.ggamma, ctx.gbeta, ctx.has_res and not masked, relu_mask=ctx.relu_mask,
@@ -953,7 +666,7 @@ class _BN(torch.autograd.Function):
                 ctx.link.grad = MaskedGrad(dy3.view(ctx.shape), ctx.relu_mask)
             if dxm:
                 dxo = dx.reshape(ctx.shape)
-                _tag_planes(dxo, out[2].view((K, 2) + tuple(ctx.shape[1:])), True)
+                tag(dxo, planes=out[2].view((K, 2) + tuple(ctx.shape[1:])), planes_only=True)
                 dres = dpre.reshape(ctx.shape) if (ctx.has_res and not masked) else None
                 if dres is not None and ctx.link is not None:
                     ctx.link.grad = dres
@@ -967,20 +680,13 @@ class _BN(torch.autograd.Function):
             dres = None
         dxo = dx.reshape(ctx.shape)
         if be is not ref:
-            dxo._dls_owned = True  # (freshly written, read by nothing else: a consumer may reuse it in place)
+            tag(dxo, owned=True)  # (freshly written, read by nothing else: a consumer may reuse it in place)
         return dxo, None, None, None, None, None, None, None, dres, None, None, None
 
 
 def batch_norm(x, token, gamma, beta, ggamma, gbeta, valid_rows=None, relu=False, residual=None,
-               link: ResidualLink | None = None, stats: BNStats | None = None, planes: int = 0):
-    """`planes` (fp32 native): 1 = the output also carries its split planes (`_dls_planes`) for
-    the conv(s) that read it, 2 = the output is ONLY planes — for outputs read by nothing but
-    split-plane convs (e.g. a ResNet block's inner BN), 3 = as 2 with the apply pass deferred to
-    the ONE conv that reads it (DeferredBN: a 3x3 stride-1 halo conv applies it while staging);
-    4 (no ReLU): the output's one reader is the next BatchNorm, as its residual, which folds this
-    apply into its own (DeferredRes: a ResNet downsample shortcut); 5: as 3 with a second reader,
-    the next BatchNorm, which takes the output as its residual and folds this apply (with its ReLU)
-    into its own (DeferredStemBN: the CIFAR ResNet stem before an identity-shortcut block)."""
+               link: ResidualLink | None = None, stats: BNStats | None = None, planes: BNOut | int = BNOut.FP32):
+    """`planes` (fp32 native): the form the output's readers take, a BNOut (ops.fusion) or its value."""
     return _BN.apply(x, token, gamma, beta, ggamma, gbeta, valid_rows, relu, residual, link, stats, planes)
 
 
@@ -998,7 +704,7 @@ class _LN(torch.autograd.Function):
         ctx.save_for_backward(x, mean, rstd, gamma)
         ctx.ggamma, ctx.gbeta = ggamma, gbeta
         if yp is not None:
-            _tag_planes(y, yp, False)
+            tag(y, planes=yp)
         return y
 
     @staticmethod
@@ -1013,7 +719,7 @@ class _LN(torch.autograd.Function):
 
 
 def layer_norm(x, token, gamma, beta, ggamma, gbeta, planes: bool = False):
-    """`planes` (fp32 native): the output also carries its split planes (`_dls_planes`) for the
+    """`planes` (fp32 native): the output also carries its split planes (tags(y).planes) for the
     split-plane linears that read it (Fn.linear)."""
     return _LN.apply(x, token, gamma, beta, ggamma, gbeta, planes)
 
@@ -1040,7 +746,7 @@ class _GN(torch.autograd.Function):
         ctx.G, ctx.valid, ctx.relu, ctx.has_res, ctx.link = G, valid, relu, residual is not None, link
         ctx.ggamma, ctx.gbeta = ggamma, gbeta
         if yp is not None:
-            _tag_planes(y, yp, False)
+            tag(y, planes=yp)
         return y
 
     @staticmethod
@@ -1065,7 +771,7 @@ def group_norm(x, token, gamma, beta, ggamma, gbeta, G: int, valid=None, relu=Fa
     sample, group), then + `residual`, then ReLU (ops.ref.gn_fwd is the contract). `valid` [K]: the
     samples b >= valid[k] are not read and come out as zeros. `link`: the residual's gradient is
     deposited there for the block's first conv instead of returned to autograd (as batch_norm).
-    `planes` (fp32 native): the output also carries its split planes (`_dls_planes`) for the
+    `planes` (fp32 native): the output also carries its split planes (tags(y).planes) for the
     split-plane convs that read it."""
     return _GN.apply(x, token, gamma, beta, ggamma, gbeta, G, valid, relu, residual, link, planes)
 
@@ -1396,7 +1102,7 @@ class _DenseBlock(torch.autograd.Function):
         g, c0 = ctx.growth, ctx.c0
         # the block's gradient buffer: the incoming gradient itself when it is a BatchNorm backward's
         # fresh output (the transition / final BN: dF_out's only reader is this backward), else a copy
-        if native and getattr(dF_out, "_dls_owned", False) and dF_out.is_contiguous():
+        if native and tags(dF_out).owned and dF_out.is_contiguous():
             dF = dF_out
             dense_grad_reuse["reused"] += 1
         else:

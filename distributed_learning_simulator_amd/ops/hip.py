@@ -358,7 +358,7 @@ def conv_dgrad(dy, w, in_hw, stride: int, pad: int, acc=None, w_split=None, dy_p
     if B * per_sample >= WINDOW and dy_planes is None:
         assert bnb is None
         if acc_mask is not None:  # (chunked launches: the gated acc built once)
-            from .functional import MaskedGrad
+            from .fusion import MaskedGrad
 
             acc, acc_mask = MaskedGrad(acc, acc_mask).dense(), None
         if acc_compact:  # (chunked launches take the full-size acc)
@@ -660,7 +660,7 @@ def linear_dgrad(dy, w, gate=None, gate_scale: float = 1.0, w_split=None, dy_pla
     dropout folded into that ReLU output). `dy_planes` [K, 2, N, Fo] (fp32, with `w_split`): dY's
     split planes — the LDS-DMA plane GEMM with the k-major weight; `out_planes`: the epilogue also
     writes dX's planes (returns (dx, planes)). `acc` [K, N, Fi] (contiguous): a second gradient of
-    X added in the epilogue (a residual branch's, ops.functional.ResidualLink)."""
+    X added in the epilogue (a residual branch's, ops.fusion.ResidualLink)."""
     K, N, Fo = dy.shape
     dy = dy.contiguous()
     f32 = _f32(dy)
@@ -745,14 +745,15 @@ def linear_wgrad(dy, x, gw, gb=None, dy_planes=None, x_planes=None, sgd=None) ->
 def planes_buffer(shape, device):
     """(fp32 tensor of `shape`, its bytes as [K, 2, *shape[1:]] bf16 split planes): client k's
     hi plane then lo plane occupy exactly the bytes of its fp32 row, so a producer that writes
-    only the planes can hand autograd the fp32-typed alias (consumers read `_dls_planes`)."""
+    only the planes can hand autograd the fp32-typed alias (consumers read its `planes` tag, ops.fusion.Tags)."""
     buf = torch.empty(shape, dtype=F32, device=device)
     K = shape[0]
     return buf, buf.view(K, -1).view(BF16).view((K, 2) + tuple(shape[1:]))
 
 
 def _planes_out(shape, device, planes: int):
-    """(fp32 output, its [K, 2, *shape[1:]] split planes) of a producer's `planes` mode: 1 = the
+    """(fp32 output, its [K, 2, *shape[1:]] split planes) of a producer's `planes` mode (the kernel
+    level's 0 / 1 / 2 of bn_fwd and dropout_apply, not ops.fusion.BNOut): 1 = the
     kernel writes both, 2 = the planes only (the output is their fp32-typed alias, planes_buffer)."""
     if planes == 2:
         return planes_buffer(shape, device)

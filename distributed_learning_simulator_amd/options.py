@@ -53,14 +53,14 @@ class RuntimeOptions:
     """BN backward partial sums from the consuming conv's dgrad epilogue (off: own reduction)."""
     bn_fused_halo: bool = dataclasses.field(default_factory=lambda: _env_bool("DLS_BN_FUSED_HALO", True))
     """A BN(+ReLU) whose only reader is a 3x3 stride-1 conv (ResNet BasicBlock bn1) is applied in
-    that conv's halo loader (ops.functional DeferredBN; off: BN apply pass + plane conv)."""
+    that conv's halo loader (ops.fusion DeferredBN; off: BN apply pass + plane conv)."""
     bn_res_fold: bool = dataclasses.field(default_factory=lambda: _env_bool("DLS_BN_RES_FOLD", True))
     """A ResNet downsample shortcut's BN is applied inside the block's last BN apply, which reads
-    its raw input as the residual (ops.functional DeferredRes; off: its own apply pass)."""
+    its raw input as the residual (ops.fusion DeferredRes; off: its own apply pass)."""
     bn_stem_defer: bool = dataclasses.field(default_factory=lambda: _env_bool("DLS_BN_STEM_DEFER", True))
     """The CIFAR ResNet stem BN(+ReLU), read by layer1.0.conv1 (planes) and by layer1.0.bn2 (fp32, as
     its identity residual), is applied by those two readers: the conv in its halo loader, the BN
-    in its residual fold (ops.functional DeferredStemBN; off: one apply pass writes both forms)."""
+    in its residual fold (ops.fusion DeferredStemBN; off: one apply pass writes both forms)."""
     dense_bn_halo: bool = dataclasses.field(default_factory=lambda: _env_bool("DLS_DENSE_BN_HALO", True))
     """DenseNet growth convs apply their BN + ReLU in the halo loader over the block buffer's
     channel prefix (off: BN apply pass + implicit-GEMM conv)."""
@@ -71,11 +71,11 @@ class RuntimeOptions:
     """A training BN(+ReLU) whose input gradient feeds only a 3x3 stride-1 conv's backward (ResNet
     BasicBlock bn1 / identity-block bn2, layers 1-3) computes its coefficients only: that conv's halo
     weight gradient applies the BN backward in its dY loader and writes dX's planes for the dgrad
-    (ops.functional DeferredBNBwd; off: the BN backward's own apply pass writes them)."""
+    (ops.fusion DeferredBNBwd; off: the BN backward's own apply pass writes them)."""
     bn_bwd_in_wgrad_f32: bool = dataclasses.field(default_factory=lambda: _env_bool("DLS_BN_BWD_IN_WGRAD_F32", True))
     """A training BN(+ReLU) behind a conv whose input needs no gradient (the ResNet stem) computes
     its backward coefficients only: the conv's fp32 weight gradient applies the BN backward in its dY
-    loader (ops.functional DeferredBNBwdF32, csrc/conv_f32.hip; off: the BN backward's own apply pass
+    loader (ops.fusion DeferredBNBwd f32, csrc/conv_f32.hip; off: the BN backward's own apply pass
     writes dX and the weight gradient reads it back)."""
     dense_wgrad_halo: bool = dataclasses.field(default_factory=lambda: _env_bool("DLS_DENSE_WGRAD_HALO", True))
     """DenseNet growth-conv weight gradients on the LDS-halo kernel (the normalised prefix staged

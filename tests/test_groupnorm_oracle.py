@@ -152,6 +152,6 @@ def test_functional_group_norm_cpu():
     Fn.group_norm(xb, token, gamma, beta, gg, gb, G, valid, True, rb, link=link).backward(dy)
     assert rb.grad is None and torch.equal(link.grad, dres) and torch.equal(xb.grad, dx)
     only = x.clone()
-    only._dls_planes_only = True
+    Fn.tag(only, planes_only=True)
     with pytest.raises(RuntimeError, match="planes-only"):
         Fn.group_norm(only, token, gamma, beta, gg, gb, G)
